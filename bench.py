@@ -13,6 +13,13 @@ MPI_Op HBM GB/s".
 A step is one pass of the hot path over one batch of synthetic input that is
 already resident in HBM.  Timing: W untimed warmup steps, barrier +
 synchronize, K timed steps, barrier + synchronize, max over ranks.
+
+A plain run does only that: set up, warm up, time the K steps, write the
+outputs if --dump-outputs is given, print the result line.  --full adds
+everything else the line can carry: the CPU baselines and the side rows
+(N = 1: next_rows_n1, config_rows_n1; N > 1: the per-phase roofline pass, the
+headline scheme's exactness check, the RCCL comparator, schemes, check, sweep,
+config5, variants, copy_nt, next_rows, p2p_osc).
 """
 from __future__ import annotations
 
@@ -43,12 +50,22 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--op-bytes", type=int, default=1 << 30, help="bytes per op buffer (N=1)")
     p.add_argument("--ar-bytes", type=int, default=256 << 20, help="allreduce bytes (N>1)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what is beside the headline: the CPU baselines and the side rows")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                        "(a fixed seeded sample of an output over 16 MiB)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-extras", action="store_true",
-                   help="N>1: skip the exactness check, size sweep and configs[4] collectives; "
+                   help="with --full: N>1: skip the exactness check, size sweep and configs[4] collectives; "
                         "N=1: skip the one-sided / point-to-point rows")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extras = True
+    return args
 
 
 def host_cpu() -> dict:
@@ -116,6 +133,9 @@ def bench_op(args):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # events on the launch stream
+    if args.dump_outputs:
+        from ompi_amd import coll_bench
+        coll_bench.dump_outputs(args.dump_outputs, {"op_sum_out": out})
     algo_bytes = 3.0 * n * 4
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
     res = {

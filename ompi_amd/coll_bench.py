@@ -86,6 +86,37 @@ def _timed(fn, steps, warmup, dist, torch, dev="cuda"):
     return float(t.item())
 
 
+DUMP_WHOLE_BYTES = 16 << 20     # an output up to this size is dumped whole
+DUMP_SAMPLE = 1 << 22           # elements kept of a larger one (16 MiB of fp32)
+DUMP_EDGE = 4096                # its first and last elements are always kept
+
+
+def dump_outputs(directory, arrays):
+    """bench.py --dump-outputs: write each named device tensor of the timed
+    path's last step as <directory>/<name>.npy (float32, or float64 for a
+    64-bit result).  A tensor over DUMP_WHOLE_BYTES is reduced to a fixed
+    sample: its first and last DUMP_EDGE elements and DUMP_SAMPLE positions
+    drawn by numpy's default_rng(20261015) from its flattened length, in
+    ascending order, so two builds given the same arguments write arrays
+    that compare element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        assert t.is_floating_point(), f"{name}: {t.dtype} has no exact float32 / float64 form"
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n * flat.element_size() > DUMP_WHOLE_BYTES:
+            rng = np.random.default_rng(20261015)
+            idx = np.concatenate([np.arange(DUMP_EDGE), np.sort(rng.integers(0, n, DUMP_SAMPLE)),
+                                  np.arange(n - DUMP_EDGE, n)])
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        host = flat.cpu().numpy()
+        host = host.astype(np.float64 if host.dtype.itemsize > 4 else np.float32, copy=False)
+        np.save(os.path.join(directory, name + ".npy"), host)
+
+
 def _settle(comm, fn, torch, limit=96):
     """Run a blocking allreduce until the library's autotune of its size
     bucket has decided (autotune_state 2), or it does not tune this size
@@ -187,17 +218,25 @@ def bench_allreduce(args, metric: str, link_gbs: float):
     _progress(rank, f"headline: {best_name}")
     t = _timed(ours, args.steps, args.warmup, dist, torch, tdev)
     err = comm.error()
-    # per-phase kernel time over one more profiled pass of K steps
-    comm.set_param("profile", 1)
-    for _ in range(args.steps):
-        ours()
-    torch.cuda.synchronize()
-    comm.set_param("profile", 0)
-    phases = [comm.phase_ms(k) for k in range(3)]  # fold, gather, scatter: (ms total, calls)
-    default_exact = _exact_ok(comm, dist, torch, mop, n, rank, shared)
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"allreduce_out": y})  # rank 0's result of the last timed step
+    # what follows takes runs of its own, so only --full has it; a plain run
+    # reports roofline.phases, bit_exact_dataset_E and rccl_comparator as None
+    full = bool(getattr(args, "full", False))
+    phases = [(0.0, 0)] * 3
+    default_exact = None
+    if full:
+        # per-phase kernel time over one more profiled pass of K steps
+        comm.set_param("profile", 1)
+        for _ in range(args.steps):
+            ours()
+        torch.cuda.synchronize()
+        comm.set_param("profile", 0)
+        phases = [comm.phase_ms(k) for k in range(3)]  # fold, gather, scatter: (ms total, calls)
+        default_exact = _exact_ok(comm, dist, torch, mop, n, rank, shared)
 
     t_rccl = None
-    if not shared:
+    if full and not shared:
         rccl_buf = x.clone()
 
         def rccl():
@@ -283,11 +322,12 @@ def bench_allreduce(args, metric: str, link_gbs: float):
                      # kernels (they meet at device barriers), so no per-
                      # launch figure of one rank exists to commit
                      "traffic_source": ("profiles/pmc.json" if traffic is not None else
+                                        "none: the per-phase pass runs with --full" if not full else
                                         "none: no dedicated-GPU PMC pass (shared-GPU counters "
                                         "mix the ranks' concurrent kernels)"),
                      "kernel": kernel,
                      "phase": dom, "kernel_ms": xg[dom]["kernel_ms"] if dom else None,
-                     "phases": ph,
+                     "phases": ph if full else None,
                      "busbw_frac_of_R": None if shared else round(busbw / roof, 4)},
         "rccl_comparator": ({"busbw": round(busbw_rccl, 2), "unit": "GB/s",
                              "ms_per_step": round(t_rccl * 1e3 / args.steps, 4)}

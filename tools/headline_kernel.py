@@ -26,7 +26,7 @@ def main():
     out = {"kernel": KERNEL, "grid_threads": g, "launches": len(durs), "avg_ns": avg,
            "min_ns": min(durs), "max_ns": max(durs), "algorithmic_bytes": ALG_BYTES,
            "achieved_GBps": ALG_BYTES / avg, "frac_of_8TBs": ALG_BYTES / avg / 8000.0,
-           "source": "rocprofv3 --kernel-trace of python3 bench.py --no-cpu-baseline, "
+           "source": "rocprofv3 --kernel-trace of python3 bench.py --full --no-cpu-baseline, "
                      "headline-grid launches only"}
     text = json.dumps(out)
     if len(sys.argv) > 2:
