@@ -314,6 +314,43 @@ int ompi_amd_allgather(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf,
 int ompi_amd_bcast(ompi_amd_comm_t *comm, void *buf, size_t bytes, int root,
                    void *stream);
 
+/* MPI_Alltoall / MPI_Alltoallv (coll_alltoall / coll_alltoallv and their
+ * nonblocking and persistent forms in coll.h).  Counts and displacements
+ * are BYTES, `size` entries each, and are copied at post / init.  Block
+ * p -> q moves by p's store into q's library memory (scratch half or landing
+ * buffer, slot [p]) and q's copy from there into rbuf: one fused launch while
+ * size * bytes_per_peer <= fused_bytes, copy / barrier / copy while
+ * bytes_per_peer <= small_bytes, else through the landing buffers — in
+ * passes of "alltoall_chunk" bytes per pair (set_param / get_param; default:
+ * what the IPC allocation cap allows `size` slots of; get_param
+ * "alltoall_passes" counts the passes run).  MPI_IN_PLACE (sbuf == rbuf or
+ * (void *)1) uses rcounts / rdispls on both sides.  alltoallv picks its path
+ * from the largest pair of the whole call, which the ranks agree on first:
+ * one host allgather in the blocking call, a posted ticket in ialltoallv
+ * (launched by progress once every peer posted), once at alltoallv_init (which
+ * is therefore collective; alltoall_init is local).  ialltoall and every plan
+ * start make no host rendezvous.  Requests and plans (kind 4) are the types
+ * above.  ompi_amd_alltoall_wait is the blocking form on the per-thread
+ * stream, as ompi_amd_allreduce_wait: a fused call stores its own
+ * host-observed completion. */
+int ompi_amd_alltoall(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes_per_peer,
+                      void *stream);
+int ompi_amd_alltoall_wait(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf,
+                           size_t bytes_per_peer);
+int ompi_amd_alltoallv(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                       const size_t *sdispls, void *rbuf, const size_t *rcounts,
+                       const size_t *rdispls, void *stream);
+int ompi_amd_ialltoall(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes_per_peer,
+                       void *stream, ompi_amd_request_t **request);
+int ompi_amd_ialltoallv(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                        const size_t *sdispls, void *rbuf, const size_t *rcounts,
+                        const size_t *rdispls, void *stream, ompi_amd_request_t **request);
+int ompi_amd_alltoall_init(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf,
+                           size_t bytes_per_peer, ompi_amd_plan_t **plan);
+int ompi_amd_alltoallv_init(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                            const size_t *sdispls, void *rbuf, const size_t *rcounts,
+                            const size_t *rdispls, ompi_amd_plan_t **plan);
+
 #ifdef __cplusplus
 }
 #endif

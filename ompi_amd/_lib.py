@@ -218,6 +218,22 @@ PROTOTYPES = [
      [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
     ("ompi_amd_bcast", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_void_p]),
+    ("ompi_amd_alltoall", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
+    ("ompi_amd_alltoall_wait", _C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t]),
+    ("ompi_amd_alltoallv", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+      _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p]),
+    ("ompi_amd_ialltoall", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_void_p)]),
+    ("ompi_amd_ialltoallv", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+      _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p, _C.POINTER(_C.c_void_p)]),
+    ("ompi_amd_alltoall_init", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.POINTER(_C.c_void_p)]),
+    ("ompi_amd_alltoallv_init", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+      _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_void_p)]),
     # point-to-point (include/ompi_amd_p2p.h)
     ("ompi_amd_isend", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,

@@ -12,6 +12,8 @@ Mirrors the coll framework's entry points this path provides
     coll_scan / coll_exscan(sbuf, rbuf, count, dtype, op, comm, module)
     coll_allgather(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, module)
     coll_bcast(buf, count, dtype, root, comm, module)
+    coll_alltoall(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, module)
+    coll_alltoallv(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm, module)
 
 with the communicator object holding the module state (IPC mappings, flags,
 epoch).  One process per GPU on one node.  All calls are stream-ordered;
@@ -209,7 +211,65 @@ class Communicator:
         rc = self._lib.ompi_amd_bcast(self._h, _ptr(buf), nbytes, root, _stream(stream))
         self._finish(rc, "bcast", blocking, stream)
 
+    def _sizes(self, values):
+        return (ctypes.c_size_t * self.size)(*[int(v) for v in values])
+
+    def _v_args(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls):
+        """alltoallv's operands; IN_PLACE takes no send-side counts."""
+        none = ctypes.POINTER(ctypes.c_size_t)()
+        return (_ptr(sbuf), none if scounts is None else self._sizes(scounts),
+                none if sdispls is None else self._sizes(sdispls), _ptr(rbuf),
+                self._sizes(rcounts), self._sizes(rdispls))
+
+    def alltoall(self, sbuf, rbuf, nbytes: int, stream=None, blocking: bool = False) -> None:
+        """MPI_Alltoall: `nbytes` per pair; block q of sbuf goes to rank q,
+        block p of rbuf comes from rank p (sbuf IN_PLACE: both in rbuf)."""
+        rc = self._lib.ompi_amd_alltoall(self._h, _ptr(sbuf), _ptr(rbuf), nbytes, _stream(stream))
+        self._finish(rc, "alltoall", blocking, stream)
+
+    def alltoall_wait(self, sbuf, rbuf, nbytes: int) -> None:
+        """MPI_Alltoall's blocking form on the per-thread stream (a fused
+        call stores its own completion mark)."""
+        _lib.check(self._lib.ompi_amd_alltoall_wait(self._h, _ptr(sbuf), _ptr(rbuf), nbytes),
+                   "alltoall_wait")
+
+    def alltoallv(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, stream=None,
+                  blocking: bool = False) -> None:
+        """MPI_Alltoallv with counts and displacements in bytes (sbuf
+        IN_PLACE: rcounts / rdispls describe both sides)."""
+        rc = self._lib.ompi_amd_alltoallv(self._h, *self._v_args(sbuf, scounts, sdispls, rbuf, rcounts,
+                                                                 rdispls), _stream(stream))
+        self._finish(rc, "alltoallv", blocking, stream)
+
     # -- nonblocking forms (coll.h:261-410) -----------------------------------
+    def ialltoall(self, sbuf, rbuf, nbytes: int, stream=None) -> "Request":
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.ompi_amd_ialltoall(self._h, _ptr(sbuf), _ptr(rbuf), nbytes,
+                                                _stream(stream), ctypes.byref(h)), "ialltoall")
+        return Request(self, h, "ialltoall")
+
+    def ialltoallv(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, stream=None) -> "Request":
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.ompi_amd_ialltoallv(self._h, *self._v_args(sbuf, scounts, sdispls, rbuf,
+                                                                        rcounts, rdispls),
+                                                 _stream(stream), ctypes.byref(h)), "ialltoallv")
+        return Request(self, h, "ialltoallv")
+
+    def alltoall_init(self, sbuf, rbuf, nbytes: int) -> "Plan":
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.ompi_amd_alltoall_init(self._h, _ptr(sbuf), _ptr(rbuf), nbytes,
+                                                    ctypes.byref(h)), "alltoall_init")
+        return Plan(self, h, "alltoall")
+
+    def alltoallv_init(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls) -> "Plan":
+        """MPI_Alltoallv_init: collective (the ranks agree on the largest
+        pair once); the starts make no host rendezvous."""
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.ompi_amd_alltoallv_init(self._h, *self._v_args(sbuf, scounts, sdispls, rbuf,
+                                                                            rcounts, rdispls),
+                                                     ctypes.byref(h)), "alltoallv_init")
+        return Plan(self, h, "alltoallv")
+
     def ireduce_scatter_block(self, sbuf, rbuf, rcount: int, datatype: Datatype, op: Op,
                               stream=None) -> "Request":
         h = ctypes.c_void_p()

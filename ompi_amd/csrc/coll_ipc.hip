@@ -377,6 +377,17 @@ struct shadow_set {
     char *mem2 = nullptr;  //   its result region when input + result exceed one allocation
 };
 
+// One alltoall / alltoallv as every path sees it: bytes, MPI_IN_PLACE
+// resolved (the send side is then the receive side, as MPI defines).
+struct a2a_call {
+    const char *sbuf;
+    char *rbuf;
+    bool inplace;
+    bool uniform;  // alltoall: both ends know both offsets of a block (the phase rule)
+    size_t B;      // uniform: bytes per pair
+    size_t sc[kMaxRanks], sd[kMaxRanks], rc[kMaxRanks], rd[kMaxRanks];
+};
+
 // A nonblocking collective posted but not launched yet.  Device work must
 // enter every rank's stream in the same order (the epoch barriers pair by
 // count), so deferred calls launch strictly first-in first-out, and every
@@ -410,10 +421,15 @@ struct pending_op {
     char *grow = nullptr;
     size_t grow_bytes = 0;
     uint64_t grow_token = 0;
+    // PEND_ALLTOALL: the call, its agreed largest pair (a2a_M; with a ticket
+    // the largest of the posted local ones instead) and the pass size
+    a2a_call a2a{};
+    size_t a2a_M = 0;
+    size_t a2a_chunk = 0;
 };
 
 enum { PEND_ALLREDUCE = 0, PEND_RSB = 1, PEND_ALLGATHER = 2, PEND_BCAST = 3, PEND_REDUCE = 4,
-       PEND_SCAN = 5, PEND_RS = 6, PEND_GROW = 7 };
+       PEND_SCAN = 5, PEND_RS = 6, PEND_GROW = 7, PEND_ALLTOALL = 8 };
 
 }  // namespace ompi_amd
 
@@ -608,6 +624,12 @@ struct ompi_amd_comm {
     // param "land_blocking" (0): blocking allgather / bcast of a zero-copy
     // size take the landing path too (an A/B the 8-GPU bench measures)
     int land_blocking = 0;
+    // param "alltoall_chunk": bytes per pair and pass of the alltoall's
+    // landing path (0: the most the IPC allocation cap allows N slots of);
+    // alltoall_passes counts the passes run
+    size_t alltoall_chunk = 0;
+    int64_t alltoall_passes = 0;
+    int64_t alltoall_paths[5] = {};  // calls per path (A2A_*), get_param "alltoall_fused" / _staged / _landing
     // param "copy_nt": 1 the copy and fold kernels store non-temporally —
     // measured no slower on one GPU at N = 2 / 4 / 8 (scatter, gather and fold
     // kernels 1-5 % faster) — 0 plain stores; -1 (default)
@@ -688,6 +710,8 @@ struct ompi_amd_plan {
     size_t bytes = 0;
     bool exclusive = false;        // PEND_SCAN: exscan
     std::vector<size_t> rcounts;   // PEND_RS: the init's counts
+    ompi_amd::a2a_call a2a{};      // PEND_ALLTOALL: the init's call and agreed largest pair
+    size_t a2a_M = 0;
     ompi_amd_request *req = nullptr;
 };
 
@@ -2811,7 +2835,10 @@ static int bcast_impl(ompi_amd_comm_t *c, void *buf, const void *root_src, size_
 static int allgather_land(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes,
                           hipStream_t s);
 static int bcast_land(ompi_amd_comm_t *c, void *buf, size_t bytes, int root, hipStream_t s);
+static size_t a2a_chunk_of(const ompi_amd_comm_t *c);
 static size_t ag_landing_need(const ompi_amd_comm_t *c, size_t bytes);
+static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const path_params &pp,
+                        size_t chunk, bool may_grow, hipStream_t s);
 static size_t bcast_landing_need(const ompi_amd_comm_t *c, size_t bytes);
 static int reduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,
                        int op, int root, bool root_inplace, hipStream_t s);
@@ -2944,6 +2971,25 @@ static void req_event_put(ompi_amd_comm_t *c, hipEvent_t ev) {
     if (ev) c->req_ev_free.push_back(ev);
 }
 
+// A deferred launch whose fused kernel may store the request's completion
+// mark itself: hand it a counter slot, run it, keep the slot only if a fused
+// kernel took it.
+template <typename F>
+static int launch_marked(ompi_amd_comm_t *c, ompi_amd_request *req, F &&launch) {
+    const int slot = req->mark ? done_slot_take(c) : -1;
+    c->want_mark = slot >= 0;
+    c->mark_word = req->mark;
+    c->mark_slot = std::max(slot, 0);
+    c->mark_embedded = 0;
+    const int rc = launch();
+    c->want_mark = false;
+    req->embedded = c->mark_embedded;
+    c->mark_embedded = 0;
+    if (req->embedded) req->done_slot = slot;
+    else done_slot_give(c, slot);  // not a fused launch: unused
+    return rc;
+}
+
 static int progress(ompi_amd_comm_t *c, bool block, int max_launch) {
     while (!c->pending.empty() && max_launch-- != 0) {
         if (c->unposted) {  // tickets the full ring held back (nb_ticket)
@@ -3028,20 +3074,21 @@ static int progress(ompi_amd_comm_t *c, bool block, int max_launch) {
                     c->force_shadow = fs;
                     break;
                 }
-                default: {
-                    // a fused launch stores the request's mark itself
-                    const int slot = o.req->mark ? done_slot_take(c) : -1;
-                    c->want_mark = slot >= 0;
-                    c->mark_word = o.req->mark;
-                    c->mark_slot = std::max(slot, 0);
-                    c->mark_embedded = 0;
-                    rc = allreduce_impl(c, o.sbuf, o.rbuf, o.count, o.type, o.op, o.stream, o.pp);
-                    c->want_mark = false;
-                    o.req->embedded = c->mark_embedded;
-                    c->mark_embedded = 0;
-                    if (o.req->embedded) o.req->done_slot = slot;
-                    else done_slot_give(c, slot);  // not a fused launch: unused
+                case PEND_ALLTOALL: {
+                    size_t M = o.a2a_M;
+                    if (o.ticket) {  // alltoallv: the largest pair any rank posted
+                        M = 0;
+                        for (int p = 0; p < c->size; ++p) M = std::max<size_t>(M, all[p].flags);
+                    }
+                    rc = launch_marked(c, o.req, [&] {
+                        return alltoall_run(c, o.a2a, M, o.pp, o.a2a_chunk, false, o.stream);
+                    });
+                    break;
                 }
+                default:
+                    rc = launch_marked(c, o.req, [&] {
+                        return allreduce_impl(c, o.sbuf, o.rbuf, o.count, o.type, o.op, o.stream, o.pp);
+                    });
                 }
             }
             if (rc == OMPI_AMD_SUCCESS) rc = shadow_out(c, o.sh, o.stream);
@@ -3483,6 +3530,10 @@ int ompi_amd_comm_set_param(ompi_amd_comm_t *c, const char *key, int64_t v) {
         c->autotune = v ? 1 : 0;
     } else if (!strcmp(key, "land_blocking")) {
         c->land_blocking = v ? 1 : 0;
+    } else if (!strcmp(key, "alltoall_chunk")) {
+        // a multiple of 256 B (every pass keeps the block's phase mod 16); 0: the default
+        if (v < 0 || (v != 0 && v < 256)) return OMPI_AMD_ERR_BAD_PARAM;
+        c->alltoall_chunk = (size_t)v & ~(size_t)255;
     } else if (!strcmp(key, "copy_nt")) {
         c->copy_nt_fixed = v >= 0;
         c->copy_nt = v != 0 ? 1 : 0;
@@ -3558,6 +3609,11 @@ int ompi_amd_comm_get_param(const ompi_amd_comm_t *c, const char *key, int64_t *
     else if (!strcmp(key, "nb_tuned_copy_nt")) *v = c->nb_tuned_nt;
     else if (!strcmp(key, "landing_ag_bcast")) *v = c->land_ag_bcast;
     else if (!strcmp(key, "land_blocking")) *v = c->land_blocking;
+    else if (!strcmp(key, "alltoall_chunk")) *v = (int64_t)a2a_chunk_of(c);
+    else if (!strcmp(key, "alltoall_passes")) *v = c->alltoall_passes;
+    else if (!strcmp(key, "alltoall_fused")) *v = c->alltoall_paths[2];
+    else if (!strcmp(key, "alltoall_staged")) *v = c->alltoall_paths[3];
+    else if (!strcmp(key, "alltoall_landing")) *v = c->alltoall_paths[4];
     else if (!strcmp(key, "copy_nt")) *v = c->copy_nt;
     else if (!strcmp(key, "copy_nt_fixed")) *v = c->copy_nt_fixed;
     else if (!strcmp(key, "unsafe_exports")) *v = c->unsafe_exports;
@@ -4530,6 +4586,320 @@ static int bcast_land(ompi_amd_comm_t *c, void *buf, size_t bytes, int root, hip
     return launch_barrier(c, s);
 }
 
+// ---- alltoall / alltoallv ----
+// Block p -> q always moves by a remote STORE of p into memory of q that q
+// then copies into its rbuf: q's scratch half, slot [p] (fused: one launch,
+// per-workgroup flags; staged: copy, barrier, copy) or q's landing buffer,
+// slot [p] (copy, barrier, copy, barrier — in passes of `chunk` bytes per
+// pair when N slots of the largest pair pass the IPC allocation cap).  The
+// path is chosen from M, the largest pair of the call (alltoall: its
+// per-pair bytes; alltoallv: agreed across the ranks before the call runs)
+// and the communicator's parameters, so every rank takes the same one.
+// Inside its slot a block sits at the phase mod 16 of the receiver's rbuf
+// offset for alltoall (allgather_land's rule: both ends know p * B) and at
+// phase 0 for alltoallv (the sender does not know the receiver's
+// displacements).
+enum { A2A_NONE = 0, A2A_LOCAL = 1, A2A_FUSED = 2, A2A_STAGED = 3, A2A_LAND = 4 };
+constexpr size_t kA2avNbChunk = 1u << 20;  // landing bytes per pair an ialltoallv post makes sure of
+
+static size_t a2a_chunk_of(const ompi_amd_comm_t *c) {
+    if (c->alltoall_chunk) return c->alltoall_chunk;
+    // N slots of ag_land_slot(chunk) under ag_landing_need's cap
+    return ((kMaxIpcBytes - (64u << 20)) / (size_t)std::max(1, c->size) / 256 - 1) * 256;
+}
+
+static int a2a_path(const ompi_amd_comm_t *c, const path_params &pp, size_t M) {
+    if (M == 0) return A2A_NONE;
+    if (c->size == 1) return A2A_LOCAL;
+    const size_t n = (size_t)c->size;
+    const bool fits = M <= c->scratch_bytes && ag_land_slot(M) * n <= c->scratch_bytes;
+    if (fits && n * M <= pp.fused_bytes) return A2A_FUSED;
+    if (fits && M <= pp.small_bytes) return A2A_STAGED;
+    return A2A_LAND;
+}
+
+static size_t a2a_phase(const a2a_call &k, int sender) {
+    return k.uniform ? ((size_t)sender * k.B) & 15 : 0;
+}
+
+static void a2a_uniform(const ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t B, a2a_call *k) {
+    *k = a2a_call{};
+    k->inplace = in_place(sbuf, rbuf);
+    k->sbuf = (const char *)(k->inplace ? rbuf : sbuf);
+    k->rbuf = (char *)rbuf;
+    k->uniform = true;
+    k->B = B;
+    for (int p = 0; p < c->size; ++p) {
+        k->sc[p] = k->rc[p] = B;
+        k->sd[p] = k->rd[p] = (size_t)p * B;
+    }
+}
+
+static void a2a_vector(const ompi_amd_comm_t *c, const void *sbuf, const size_t *sc, const size_t *sd,
+                       void *rbuf, const size_t *rc, const size_t *rd, a2a_call *k) {
+    *k = a2a_call{};
+    k->inplace = in_place(sbuf, rbuf);
+    k->sbuf = (const char *)(k->inplace ? rbuf : sbuf);
+    k->rbuf = (char *)rbuf;
+    for (int p = 0; p < c->size; ++p) {
+        k->rc[p] = rc[p];
+        k->rd[p] = rd[p];
+        k->sc[p] = k->inplace ? rc[p] : sc[p];
+        k->sd[p] = k->inplace ? rd[p] : sd[p];
+    }
+}
+
+// the largest pair this rank sees: its row and its column of the count matrix
+static size_t a2a_local_max(const ompi_amd_comm_t *c, const a2a_call &k) {
+    size_t m = 0;
+    for (int p = 0; p < c->size; ++p) m = std::max(m, std::max(k.sc[p], k.rc[p]));
+    return m;
+}
+
+static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipStream_t s) {
+    note_stream(c, s);
+    const int n = c->size, me = c->rank;
+    const stage_half sh = next_half(c);
+    a2a_args a{};
+    a.sbuf = k.sbuf;
+    a.rbuf = k.rbuf;
+    a.mine = sh.mine;
+    a.peers = sh.peers;
+    a.flags = c->flags;
+    a.peer_flags = c->peer_flags;
+    a.rank = me;
+    a.n = n;
+    a.self_copy = k.inplace ? 0 : 1;
+    a.slot = (int64_t)ag_land_slot(M);
+    for (int p = 0; p < n; ++p) {
+        a.scount[p] = (int64_t)k.sc[p];
+        a.sdispl[p] = (int64_t)k.sd[p];
+        a.rcount[p] = (int64_t)k.rc[p];
+        a.rdispl[p] = (int64_t)k.rd[p];
+        a.sphase[p] = (uint8_t)a2a_phase(k, me);
+        a.rphase[p] = (uint8_t)a2a_phase(k, p);
+    }
+    a.epoch = ++c->epoch;
+    a.timeout_ticks = (uint64_t)c->timeout_ms * 100000ull;  // s_memrealtime: 100 MHz
+    a.err = c->err_dev;
+    // the grid from M alone: both ends of a pair cut its block alike (a2a_slice)
+    const unsigned groups = (unsigned)std::max<size_t>(
+        1, std::min<size_t>((M + 16 * kXferThreads - 1) / (16 * kXferThreads), kFusedMaxGroups));
+    if (c->want_mark && c->mark_word) {  // the call's completion, by the kernel itself
+        a.done = reinterpret_cast<uint32_t *>(c->flags) + kFusedDoneWord + kFusedDoneStride * c->mark_slot;
+        a.mark = c->mark_word;
+        a.mark_v = mark_reserve();
+    }
+    if (c->copy_nt)
+        hipLaunchKernelGGL(fused_alltoall_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(fused_alltoall_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, a);
+    TRY(record_hip(hipGetLastError(), "fused alltoall launch"));
+    if (a.mark) c->mark_embedded = a.mark_v;
+    return OMPI_AMD_SUCCESS;
+}
+
+// One exchange of bytes [off, off + chunk) of every pair through slots of
+// `slot` bytes: `mine` is where my peers' stores land, peers.p[q] the same
+// memory of rank q as mapped here.
+static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, size_t chunk,
+                             char *mine, const ptr_set &peers, size_t slot, bool trailing,
+                             hipStream_t s) {
+    const int n = c->size, me = c->rank;
+    auto piece = [&](size_t cnt, size_t *lo, size_t *len) {
+        *lo = std::min(cnt, off);
+        *len = std::min(cnt, off + chunk) - *lo;
+    };
+    size_t lo, len;
+    cp_jobs cj{};
+    for (int i = 0; i < n; ++i) {  // my own block, then peers rank+1, rank+2, ...
+        const int q = (me + i) % n;
+        piece(k.sc[q], &lo, &len);
+        if (!len || (i == 0 && k.inplace)) continue;
+        char *d = i == 0 ? k.rbuf + k.rd[me] + lo
+                         : const_cast<char *>(peers.p[q]) + (size_t)me * slot + a2a_phase(k, me);
+        cj.j[cj.n++] = {k.sbuf + k.sd[q] + lo, d, (int64_t)len};
+    }
+    TRY(launch_copy(c, cj, s));
+    TRY(launch_barrier(c, s));
+    cj = cp_jobs{};
+    for (int p = 0; p < n; ++p) {
+        piece(k.rc[p], &lo, &len);
+        if (!len || p == me) continue;
+        cj.j[cj.n++] = {mine + (size_t)p * slot + a2a_phase(k, p), k.rbuf + k.rd[p] + lo, (int64_t)len};
+    }
+    TRY(launch_copy(c, cj, s));
+    return trailing ? launch_barrier(c, s) : OMPI_AMD_SUCCESS;
+}
+
+static int alltoall_land(ompi_amd_comm_t *c, const a2a_call &k, size_t M, size_t chunk, bool may_grow,
+                         hipStream_t s) {
+    const size_t n = (size_t)c->size;
+    chunk = std::min(chunk, M);
+    if (n * ag_land_slot(chunk) > c->land_bytes) {
+        if (may_grow) {  // collective: every rank computes the same need
+            TRY(ensure_landing(c, n * ag_land_slot(chunk)));
+        } else {
+            // a deferred call runs in passes the landing buffer it finds can
+            // hold (the same on every rank: growths switch at one queue position)
+            const size_t per = (c->land_bytes / n) & ~(size_t)255;
+            if (per < 512) {
+                record_msg("alltoall: no landing buffer for a deferred call (%zu B)", c->land_bytes);
+                return OMPI_AMD_ERR_UNSUPPORTED;
+            }
+            chunk = std::min(chunk, per - 256);
+        }
+    }
+    const size_t slot = ag_land_slot(chunk);
+    for (size_t off = 0; off < M; off += chunk) {
+        TRY(alltoall_exchange(c, k, off, chunk, c->land, c->peer_land, slot, true, s));
+        ++c->alltoall_passes;
+    }
+    return OMPI_AMD_SUCCESS;
+}
+
+static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const path_params &pp,
+                        size_t chunk, bool may_grow, hipStream_t s) {
+    const int path = a2a_path(c, pp, M);
+    ++c->alltoall_paths[path];
+    if (path == A2A_NONE) return OMPI_AMD_SUCCESS;
+    TRY(set_dev(c));
+    if (path == A2A_LOCAL) {
+        cp_jobs cj{};
+        if (!k.inplace && k.sc[0]) cj.j[cj.n++] = {k.sbuf + k.sd[0], k.rbuf + k.rd[0], (int64_t)k.sc[0]};
+        return launch_copy(c, cj, s);
+    }
+    if (path == A2A_FUSED) return alltoall_fused(c, k, M, s);
+    if (path == A2A_STAGED) {
+        // no trailing barrier: the halves alternate (next_half)
+        const stage_half sh = next_half(c);
+        return alltoall_exchange(c, k, 0, M, sh.mine, sh.peers, ag_land_slot(M), false, s);
+    }
+    return alltoall_land(c, k, M, chunk, may_grow, s);
+}
+
+static int a2av_args_ok(const ompi_amd_comm_t *c, const void *sbuf, const size_t *sc, const size_t *sd,
+                        void *rbuf, const size_t *rc, const size_t *rd) {
+    if (!c || !rc || !rd) return OMPI_AMD_ERR_BAD_PARAM;
+    const bool inplace = in_place(sbuf, rbuf);
+    if (!inplace && (!sc || !sd)) return OMPI_AMD_ERR_BAD_PARAM;
+    for (int p = 0; p < c->size; ++p) {
+        if (rc[p] > 0 && !rbuf) return OMPI_AMD_ERR_BAD_PARAM;
+        if (!inplace && sc[p] > 0 && !sbuf) return OMPI_AMD_ERR_BAD_PARAM;
+    }
+    return OMPI_AMD_SUCCESS;
+}
+
+// alltoallv's agreement on the largest pair of the call: every rank sees
+// only its row and column of the count matrix
+static int a2av_agree(ompi_amd_comm_t *c, const a2a_call &k, size_t *M) {
+    size_t mine = a2a_local_max(c, k), all[kMaxRanks];
+    *M = mine;
+    if (c->size == 1) return OMPI_AMD_SUCCESS;
+    TRY(c->boot.allgather(&mine, all, sizeof(mine)));
+    for (int p = 0; p < c->size; ++p) *M = std::max(*M, all[p]);
+    return OMPI_AMD_SUCCESS;
+}
+
+int ompi_amd_alltoall(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream) {
+    api_guard api_(c);
+    if (!c || ((!rbuf || !sbuf) && bytes > 0)) return OMPI_AMD_ERR_BAD_PARAM;
+    TRY(check_sticky(c));
+    TRY(drain(c));
+    a2a_call k;
+    a2a_uniform(c, sbuf, rbuf, bytes, &k);
+    return alltoall_run(c, k, bytes, params_of(c), a2a_chunk_of(c), true, comm_stream(c, stream));
+}
+
+int ompi_amd_alltoall_wait(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes) {
+    if (!c) return OMPI_AMD_ERR_BAD_PARAM;
+    c->want_mark = fused_mark_on();
+    c->mark_word = c->fused_mark;
+    c->mark_slot = 0;
+    c->mark_embedded = 0;
+    const int rc = ompi_amd_alltoall(c, sbuf, rbuf, bytes, nullptr);
+    c->want_mark = false;
+    const uint64_t v = c->mark_embedded;
+    c->mark_embedded = 0;
+    if (rc != OMPI_AMD_SUCCESS || !v) return rc != OMPI_AMD_SUCCESS ? rc : ompi_amd_comm_sync(c, nullptr);
+    // the fused kernel was the call's only launch and stores the mark itself
+    api_guard api_(c);
+    TRY(record_hip(mark_value_wait(comm_stream(c, nullptr), c->fused_mark, v, progress_others), "alltoall wait"));
+    return check_sticky(c);
+}
+
+int ompi_amd_alltoallv(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                       void *rbuf, const size_t *rcounts, const size_t *rdispls, void *stream) {
+    api_guard api_(c);
+    TRY(a2av_args_ok(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls));
+    TRY(check_sticky(c));
+    TRY(drain(c));
+    a2a_call k;
+    a2a_vector(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, &k);
+    size_t M = 0;
+    TRY(a2av_agree(c, k, &M));
+    return alltoall_run(c, k, M, params_of(c), a2a_chunk_of(c), true, comm_stream(c, stream));
+}
+
+// Post one nonblocking alltoall(v).  agree: M is not known yet (ialltoallv)
+// — the post carries this rank's largest pair as a ticket, and progress
+// launches the call with the largest of all once every peer has posted.
+// The landing path posts no buffer descriptor, so a call with a known M
+// launches from the post itself; its landing buffer is grown (deferred)
+// at post time.  An ialltoallv cannot size that growth, so its post makes
+// sure of kA2avNbChunk bytes per pair and the launch runs in passes of
+// what the buffer it finds holds.
+static int ia2a_post(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree, void *stream,
+                     ompi_amd_request_t **out) {
+    *out = nullptr;
+    ompi_amd_request *req = nullptr;
+    TRY(nb_begin(c, &req));
+    pending_op o{0, k.sbuf, k.rbuf, 0, 0, 0, comm_stream(c, stream), params_of(c), req};
+    o.kind = PEND_ALLTOALL;
+    o.a2a = k;
+    o.a2a_chunk = a2a_chunk_of(c);
+    const size_t n = (size_t)c->size;
+    if (n == 1) agree = false;
+    o.a2a_M = agree ? 0 : M;
+    size_t need = 0;
+    if (agree) need = n * ag_land_slot(std::min(o.a2a_chunk, kA2avNbChunk));
+    else if (a2a_path(c, o.pp, M) == A2A_LAND) need = n * ag_land_slot(std::min(o.a2a_chunk, M));
+    if (need) TRY(nb_grow_landing(c, need, req, o.stream));
+    if (!agree) return nb_post(c, o, nullptr, 0, false, out);
+    call_blob mine{};
+    mine.flags = (uint64_t)M;
+    const int rc = nb_ticket(c, o, &mine, sizeof(mine));
+    if (rc != OMPI_AMD_SUCCESS) {
+        req_event_put(req->c, req->ev);
+        delete req;
+        return rc;
+    }
+    c->pending.push_back(o);
+    c->npending.fetch_add(1);
+    *out = req;
+    return post_progress(c);
+}
+
+int ompi_amd_ialltoall(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream,
+                       ompi_amd_request_t **out) {
+    api_guard api_(c);
+    if (!c || !out || ((!rbuf || !sbuf) && bytes > 0)) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_uniform(c, sbuf, rbuf, bytes, &k);
+    return ia2a_post(c, k, bytes, false, stream, out);
+}
+
+int ompi_amd_ialltoallv(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts,
+                        const size_t *sdispls, void *rbuf, const size_t *rcounts, const size_t *rdispls,
+                        void *stream, ompi_amd_request_t **out) {
+    api_guard api_(c);
+    TRY(a2av_args_ok(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls));
+    if (!out) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_vector(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, &k);
+    return ia2a_post(c, k, a2a_local_max(c, k), true, stream, out);
+}
+
 int ompi_amd_allreduce_init(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count,
                             int type, int op, ompi_amd_plan_t **out) {
     api_guard api_(c);
@@ -4659,6 +5029,8 @@ static int plan_nb_post(ompi_amd_plan_t *pl, void *stream) {
     case PEND_RS:
         return ompi_amd_ireduce_scatter(c, pl->src, pl->rbuf, pl->rcounts.data(), pl->type, pl->op, stream,
                                         &pl->req);
+    case PEND_ALLTOALL:  // the largest pair was agreed at init: no ticket
+        return ia2a_post(c, pl->a2a, pl->a2a_M, false, stream, &pl->req);
     default:
         return OMPI_AMD_ERR_BAD_PARAM;
     }
@@ -4723,6 +5095,36 @@ int ompi_amd_reduce_scatter_init(ompi_amd_comm_t *c, const void *sbuf, void *rbu
     TRY(plan_nb_new(c, PEND_RS, sbuf, rbuf, 0, type, op, 0, 0, out));
     (*out)->rcounts.assign(rcounts, rcounts + c->size);
     return OMPI_AMD_SUCCESS;
+}
+
+// Persistent alltoall / alltoallv (MPI-4 MPI_Alltoall_init / MPI_Alltoallv_init).
+// alltoall_init is local; alltoallv_init is collective: the ranks agree on the
+// largest pair once, so no start exchanges anything on the host.
+int ompi_amd_alltoall_init(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes,
+                           ompi_amd_plan_t **out) {
+    api_guard api_(c);
+    if (!c || !out || ((!rbuf || !sbuf) && bytes > 0)) return OMPI_AMD_ERR_BAD_PARAM;
+    TRY(plan_nb_new(c, PEND_ALLTOALL, sbuf, rbuf, 0, 0, 0, 0, bytes, out));
+    a2a_uniform(c, sbuf, rbuf, bytes, &(*out)->a2a);
+    (*out)->a2a_M = bytes;
+    return OMPI_AMD_SUCCESS;
+}
+
+int ompi_amd_alltoallv_init(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts,
+                            const size_t *sdispls, void *rbuf, const size_t *rcounts,
+                            const size_t *rdispls, ompi_amd_plan_t **out) {
+    api_guard api_(c);
+    TRY(a2av_args_ok(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls));
+    if (!out) return OMPI_AMD_ERR_BAD_PARAM;
+    TRY(drain(c));
+    TRY(plan_nb_new(c, PEND_ALLTOALL, sbuf, rbuf, 0, 0, 0, 0, 0, out));
+    a2a_vector(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, &(*out)->a2a);
+    const int rc = a2av_agree(c, (*out)->a2a, &(*out)->a2a_M);
+    if (rc != OMPI_AMD_SUCCESS) {
+        delete *out;
+        *out = nullptr;
+    }
+    return rc;
 }
 
 static int scan_init_common(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,

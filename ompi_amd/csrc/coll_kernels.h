@@ -687,6 +687,94 @@ __global__ __launch_bounds__(kXferThreads) void pipe_allreduce_kernel(pipe_args 
     xfer_epilogue();
 }
 
+// ---------------------------------------------------------------- fused small alltoall(v)
+// One launch for small personalised exchanges (param "fused_bytes"), on the
+// fused allreduce's protocol and flag rows: workgroup g STORES its slice of
+// every block of my send buffer into the receiver's scratch half, slot
+// [me] (a remote store: posted writes, no round trip per access; the
+// allgather's landing path moves its data the same way), drains its stores,
+// releases at system scope and signals every peer on flag row g; it then
+// waits for workgroup g of every peer, acquires, and copies the same slice
+// of every slot of MY scratch half into rbuf.  Workgroup g depends only on
+// the peers' workgroup g.  The slice of block p -> q is cut from values p
+// and q hold alike: the grid (from the call's agreed largest pair) and the
+// pair's byte count.  Counts and displacements are bytes; block p -> q sits
+// in its slot at phase sphase[q] (on p) == rphase[p] (on q) mod 16, so both
+// copies run as 16-B vectors whenever their two ends share that phase.
+struct a2a_args {
+    const char *sbuf;
+    char *rbuf, *mine;   // mine: my scratch half (slot [p] holds what p sent me)
+    ptr_set peers;       // every rank's scratch half as mapped here
+    uint64_t *flags;
+    flag_set peer_flags;
+    int rank, n;
+    int self_copy;       // 0: in place, my own block stays where it is
+    int64_t slot;        // bytes per slot
+    int64_t scount[kMaxRanks], sdispl[kMaxRanks], rcount[kMaxRanks], rdispl[kMaxRanks];
+    uint8_t sphase[kMaxRanks], rphase[kMaxRanks];
+    uint64_t epoch, timeout_ticks;
+    int *err;
+    // host-observed completion by the last workgroup (fused_args)
+    uint32_t *done;
+    uint64_t *mark;
+    uint64_t mark_v;
+};
+
+// bytes [*lo, *hi) of a b-byte block that workgroup g of G moves (16-B granules)
+__host__ __device__ __forceinline__ void a2a_slice(int64_t b, int g, int G, int64_t *lo, int64_t *hi) {
+    const int64_t per = ((b + G - 1) / G + 15) & ~(int64_t)15;
+    *lo = per * g < b ? per * g : b;
+    *hi = per * (g + 1) < b ? per * (g + 1) : b;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void fused_alltoall_kernel(a2a_args a) {
+    const int t = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+    int64_t lo, hi;
+    for (int k = 0; k < a.n; ++k) {  // my own block first, then peers rank+1, rank+2, ...
+        const int q = (a.rank + k) % a.n;
+        if (k == 0 && !a.self_copy) continue;
+        a2a_slice(a.scount[q], g, G, &lo, &hi);
+        char *d = k == 0 ? a.rbuf + a.rdispl[q]
+                         : const_cast<char *>(a.peers.p[q]) + (int64_t)a.rank * a.slot + a.sphase[q];
+        pipe_copy(a.sbuf + a.sdispl[q], d, lo, hi, NT && k != 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) sys_release();
+    __syncthreads();
+    __shared__ int gave_up;
+    if (t == 0) gave_up = 0;
+    __syncthreads();
+    if (t < a.n && t != a.rank) {
+        __hip_atomic_store(a.peer_flags.p[t] + g * kMaxRanks + a.rank, a.epoch, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!wait_epoch(a.flags + g * kMaxRanks + t, a.epoch, a.err, a.timeout_ticks,
+                        a.flags + kAbortWord))
+            gave_up = 1;
+    }
+    __syncthreads();
+    if (gave_up) return;  // a peer never arrived: its slot holds nothing of this call
+    acquire_once();
+    for (int p = 0; p < a.n; ++p) {
+        if (p == a.rank) continue;
+        a2a_slice(a.rcount[p], g, G, &lo, &hi);
+        pipe_copy(a.mine + (int64_t)p * a.slot + a.rphase[p], a.rbuf + a.rdispl[p], lo, hi, false);
+    }
+    if (a.mark) {  // the host-observed completion, by the last workgroup
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (t == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            if (__hip_atomic_fetch_add(a.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
+                (uint32_t)G - 1) {
+                __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.mark, a.mark_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launch rows
 using red_launch_fn = hipError_t (*)(dim3, const ptr_set &, const ptr_set &, int, int, int, int,
                                      const red_jobs &, hipStream_t);

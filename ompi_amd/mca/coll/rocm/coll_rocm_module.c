@@ -294,6 +294,15 @@ static void rocm_module_destruct(mca_coll_rocm_module_t *m)
         OBJ_RELEASE(m->c_coll.coll_reduce_scatter_init_module);
     if (NULL != m->c_coll.coll_scan_init_module) OBJ_RELEASE(m->c_coll.coll_scan_init_module);
     if (NULL != m->c_coll.coll_exscan_init_module) OBJ_RELEASE(m->c_coll.coll_exscan_init_module);
+#ifdef ROCM_HAVE_ALLTOALL
+    if (NULL != m->c_coll.coll_alltoall_module) OBJ_RELEASE(m->c_coll.coll_alltoall_module);
+    if (NULL != m->c_coll.coll_alltoallv_module) OBJ_RELEASE(m->c_coll.coll_alltoallv_module);
+    if (NULL != m->c_coll.coll_ialltoall_module) OBJ_RELEASE(m->c_coll.coll_ialltoall_module);
+    if (NULL != m->c_coll.coll_ialltoallv_module) OBJ_RELEASE(m->c_coll.coll_ialltoallv_module);
+    if (NULL != m->c_coll.coll_alltoall_init_module) OBJ_RELEASE(m->c_coll.coll_alltoall_init_module);
+    if (NULL != m->c_coll.coll_alltoallv_init_module)
+        OBJ_RELEASE(m->c_coll.coll_alltoallv_init_module);
+#endif
     if (NULL != m->dev_comm) (void) ompi_amd_comm_destroy(m->dev_comm);
     for (int k = 0; k < 2; ++k) {
         (void) ompi_amd_device_free(m->dstage[k]);
@@ -346,6 +355,14 @@ mca_coll_base_module_t *mca_coll_rocm_comm_query(struct ompi_communicator_t *com
     m->super.coll_reduce_scatter_init = mca_coll_rocm_reduce_scatter_init;
     m->super.coll_scan_init = mca_coll_rocm_scan_init;
     m->super.coll_exscan_init = mca_coll_rocm_exscan_init;
+#ifdef ROCM_HAVE_ALLTOALL
+    m->super.coll_alltoall = mca_coll_rocm_alltoall;
+    m->super.coll_alltoallv = mca_coll_rocm_alltoallv;
+    m->super.coll_ialltoall = mca_coll_rocm_ialltoall;
+    m->super.coll_ialltoallv = mca_coll_rocm_ialltoallv;
+    m->super.coll_alltoall_init = mca_coll_rocm_alltoall_init;
+    m->super.coll_alltoallv_init = mca_coll_rocm_alltoallv_init;
+#endif
     return &m->super;
 }
 
@@ -386,6 +403,14 @@ int mca_coll_rocm_module_enable(mca_coll_base_module_t *module, struct ompi_comm
     SAVE(reduce_scatter_init);
     SAVE(scan_init);
     SAVE(exscan_init);
+#ifdef ROCM_HAVE_ALLTOALL
+    SAVE(alltoall);
+    SAVE(alltoallv);
+    SAVE(ialltoall);
+    SAVE(ialltoallv);
+    SAVE(alltoall_init);
+    SAVE(alltoallv_init);
+#endif
 #undef SAVE
 
     /* node-unique segment name: job id + communicator id */
@@ -1691,3 +1716,218 @@ int mca_coll_rocm_exscan_init(const void *sbuf, void *rbuf, int count, struct om
     return rocm_scan_init_common(sbuf, rbuf, count, dtype, op, comm, info, request,
                                  (mca_coll_rocm_module_t *) module, 1);
 }
+
+#ifdef ROCM_HAVE_ALLTOALL
+/* ------------------------------------------------------------- alltoall(v)
+ * MPI_Alltoall / MPI_Alltoallv and their nonblocking and persistent forms
+ * (coll_alltoall, coll_alltoallv, coll_ialltoall, coll_ialltoallv,
+ * coll_alltoall_init, coll_alltoallv_init), in mca_coll_rocm_allgather's
+ * shape: they move bytes, so any datatype qualifies; the vote covers
+ * residency and layout; a rank whose layout is not contiguous packs when the
+ * device path runs.  The library takes bytes: counts are count * type size,
+ * displacements disp * extent (disp * type size inside a packed operand,
+ * which is dense).  coll_rocm_max_device_mib bounds alltoall's bytes per
+ * pair; alltoallv has no size every rank computes alike (a rank sees its row
+ * and column only) and needs none: past the landing buffers' capacity the
+ * library runs in passes.  form: 0 blocking, 1 nonblocking, 2 persistent. */
+enum { A2A_BLOCKING = 0, A2A_NONBLOCKING = 1, A2A_PERSISTENT = 2 };
+
+static int rocm_a2a_begin(mca_coll_rocm_module_t *m, int form, int uniform_ok, int local_ok,
+                          rocm_operand_t *o, struct rocm_nb_stage **st, int *path)
+{
+    *st = NULL;
+    if (A2A_BLOCKING == form) return rocm_begin(m, uniform_ok, local_ok, o, 2, path);
+    return rocm_nb_begin(m, uniform_ok, local_ok, o, 2, st, path);
+}
+
+static int rocm_alltoall_common(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                                void *rbuf, int rcount, struct ompi_datatype_t *rdtype,
+                                struct ompi_communicator_t *comm, struct ompi_info_t *info,
+                                ompi_request_t **request, mca_coll_rocm_module_t *m, int form)
+{
+    const int inplace = MPI_IN_PLACE == sbuf;
+    const size_t n = (size_t) ompi_comm_size(comm);
+    rocm_operand_t o[2] = {{(void *) sbuf, (size_t) scount * n, sdtype, 1, 0},
+                           {rbuf, (size_t) rcount * n, rdtype, inplace, 1}};
+    struct rocm_nb_stage *st = NULL;
+    ompi_amd_request_t *nb = NULL;
+    ompi_amd_plan_t *plan = NULL;
+    ompi_request_t *inner = NULL;
+    size_t ssize = 0, rsize = 0, bytes;
+    int path, rc, ok, same;
+    (void) ompi_datatype_type_size(rdtype, &rsize);
+    if (!inplace) (void) ompi_datatype_type_size(sdtype, &ssize);
+    bytes = rsize * (size_t) rcount;
+    /* the uniform call moves one byte count per pair: a rank whose send and
+     * receive sides differ leaves the call to the saved function (matching
+     * type signatures make every rank decide alike, MPI-4.1 §6.4) */
+    same = (inplace || ssize * (size_t) scount == bytes) && bytes_ok(bytes);
+    ok = ompi_datatype_is_contiguous_memory_layout(rdtype, (int) (rcount * n)) && dev(rbuf) &&
+         dev(sbuf) && (inplace || ompi_datatype_is_contiguous_memory_layout(sdtype, (int) (scount * n)));
+    rc = rocm_a2a_begin(m, form, same, ok, o, &st, &path);
+    if (OMPI_SUCCESS != rc) return rc;
+    if (ROCM_DEVICE != path) {
+        if (A2A_BLOCKING == form) {
+            rc = m->c_coll.coll_alltoall(o[0].use, scount, sdtype, o[1].use, rcount, rdtype, comm,
+                                         m->c_coll.coll_alltoall_module);
+            return rocm_unstage(m, o, 2, rc);
+        }
+        rc = A2A_NONBLOCKING == form
+                 ? m->c_coll.coll_ialltoall(o[0].use, scount, sdtype, o[1].use, rcount, rdtype, comm,
+                                            &inner, m->c_coll.coll_ialltoall_module)
+                 : m->c_coll.coll_alltoall_init(o[0].use, scount, sdtype, o[1].use, rcount, rdtype,
+                                                comm, info, &inner,
+                                                m->c_coll.coll_alltoall_init_module);
+        return rocm_saved_post(rc, inner, st, comm, request);
+    }
+    sbuf = inplace ? (const void *) 1 : o[0].use;
+    if (A2A_BLOCKING == form) {
+        rc = ompi_amd_alltoall(m->dev_comm, sbuf, o[1].use, bytes, NULL);
+        return rocm_dev_finish(m, o, 2, rc);
+    }
+    if (A2A_NONBLOCKING == form) {
+        rc = ompi_amd_ialltoall(m->dev_comm, sbuf, o[1].use, bytes, NULL, &nb);
+        return rocm_nb_post(rc, nb, st, comm, request);
+    }
+    rc = ompi_amd_alltoall_init(m->dev_comm, sbuf, o[1].use, bytes, &plan);
+    return rocm_wrap_plan(rc, plan, st, comm, request);
+}
+
+/* elements an alltoallv operand spans */
+static size_t a2av_span(const int *counts, const int *disps, int n)
+{
+    size_t span = 0;
+    for (int p = 0; p < n; ++p) {
+        const size_t end = (size_t) disps[p] + (size_t) counts[p];
+        if (counts[p] > 0 && end > span) span = end;
+    }
+    return span;
+}
+
+/* int counts / element displacements of one side to bytes */
+static void a2av_bytes(const rocm_operand_t *x, struct ompi_datatype_t *dtype, const int *counts,
+                       const int *disps, int n, size_t *bc, size_t *bd)
+{
+    size_t size = 0;
+    ptrdiff_t lb, ext;
+    (void) ompi_datatype_type_size(dtype, &size);
+    (void) ompi_datatype_get_extent(dtype, &lb, &ext);
+    for (int p = 0; p < n; ++p) {
+        bc[p] = (size_t) counts[p] * size;
+        bd[p] = (size_t) disps[p] * (2 == x->how ? size : (size_t) ext);
+    }
+}
+
+static int rocm_alltoallv_common(const void *sbuf, const int *scounts, const int *sdisps,
+                                 struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
+                                 const int *rdisps, struct ompi_datatype_t *rdtype,
+                                 struct ompi_communicator_t *comm, struct ompi_info_t *info,
+                                 ompi_request_t **request, mca_coll_rocm_module_t *m, int form)
+{
+    const int inplace = MPI_IN_PLACE == sbuf;
+    const int n = ompi_comm_size(comm);
+    const size_t sspan = inplace ? 0 : a2av_span(scounts, sdisps, n);
+    const size_t rspan = a2av_span(rcounts, rdisps, n);
+    /* the receive side is read too: what lies between its blocks survives a
+     * staged copy back */
+    rocm_operand_t o[2] = {{(void *) sbuf, sspan, sdtype, 1, 0}, {rbuf, rspan, rdtype, 1, 1}};
+    struct rocm_nb_stage *st = NULL;
+    ompi_amd_request_t *nb = NULL;
+    ompi_amd_plan_t *plan = NULL;
+    ompi_request_t *inner = NULL;
+    size_t sc[OMPI_AMD_MAX_RANKS], sd[OMPI_AMD_MAX_RANKS], rc_[OMPI_AMD_MAX_RANKS],
+        rd[OMPI_AMD_MAX_RANKS];
+    int path, rc, ok;
+    ok = ompi_datatype_is_contiguous_memory_layout(rdtype, (int) rspan) && (0 == rspan || dev(rbuf)) &&
+         (inplace || 0 == sspan ||
+          (dev(sbuf) && ompi_datatype_is_contiguous_memory_layout(sdtype, (int) sspan)));
+    rc = rocm_a2a_begin(m, form, 1, ok, o, &st, &path);
+    if (OMPI_SUCCESS != rc) return rc;
+    if (ROCM_DEVICE != path) {
+        if (A2A_BLOCKING == form) {
+            rc = m->c_coll.coll_alltoallv(o[0].use, scounts, sdisps, sdtype, o[1].use, rcounts, rdisps,
+                                          rdtype, comm, m->c_coll.coll_alltoallv_module);
+            return rocm_unstage(m, o, 2, rc);
+        }
+        rc = A2A_NONBLOCKING == form
+                 ? m->c_coll.coll_ialltoallv(o[0].use, scounts, sdisps, sdtype, o[1].use, rcounts,
+                                             rdisps, rdtype, comm, &inner,
+                                             m->c_coll.coll_ialltoallv_module)
+                 : m->c_coll.coll_alltoallv_init(o[0].use, scounts, sdisps, sdtype, o[1].use, rcounts,
+                                                 rdisps, rdtype, comm, info, &inner,
+                                                 m->c_coll.coll_alltoallv_init_module);
+        return rocm_saved_post(rc, inner, st, comm, request);
+    }
+    a2av_bytes(&o[1], rdtype, rcounts, rdisps, n, rc_, rd);
+    if (!inplace) a2av_bytes(&o[0], sdtype, scounts, sdisps, n, sc, sd);
+    sbuf = inplace ? (const void *) 1 : o[0].use;
+    if (A2A_BLOCKING == form) {
+        rc = ompi_amd_alltoallv(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                                rc_, rd, NULL);
+        return rocm_dev_finish(m, o, 2, rc);
+    }
+    if (A2A_NONBLOCKING == form) {
+        rc = ompi_amd_ialltoallv(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                                 rc_, rd, NULL, &nb);
+        return rocm_nb_post(rc, nb, st, comm, request);
+    }
+    rc = ompi_amd_alltoallv_init(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                                 rc_, rd, &plan);
+    return rocm_wrap_plan(rc, plan, st, comm, request);
+}
+
+int mca_coll_rocm_alltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                           int rcount, struct ompi_datatype_t *rdtype,
+                           struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    return rocm_alltoall_common(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, NULL, NULL,
+                                (mca_coll_rocm_module_t *) module, A2A_BLOCKING);
+}
+
+int mca_coll_rocm_alltoallv(const void *sbuf, const int *scounts, const int *sdisps,
+                            struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
+                            const int *rdisps, struct ompi_datatype_t *rdtype,
+                            struct ompi_communicator_t *comm, mca_coll_base_module_t *module)
+{
+    return rocm_alltoallv_common(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
+                                 NULL, NULL, (mca_coll_rocm_module_t *) module, A2A_BLOCKING);
+}
+
+int mca_coll_rocm_ialltoall(const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf,
+                            int rcount, struct ompi_datatype_t *rdtype,
+                            struct ompi_communicator_t *comm, ompi_request_t **request,
+                            mca_coll_base_module_t *module)
+{
+    return rocm_alltoall_common(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, NULL, request,
+                                (mca_coll_rocm_module_t *) module, A2A_NONBLOCKING);
+}
+
+int mca_coll_rocm_ialltoallv(const void *sbuf, const int *scounts, const int *sdisps,
+                             struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
+                             const int *rdisps, struct ompi_datatype_t *rdtype,
+                             struct ompi_communicator_t *comm, ompi_request_t **request,
+                             mca_coll_base_module_t *module)
+{
+    return rocm_alltoallv_common(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
+                                 NULL, request, (mca_coll_rocm_module_t *) module, A2A_NONBLOCKING);
+}
+
+int mca_coll_rocm_alltoall_init(const void *sbuf, int scount, struct ompi_datatype_t *sdtype,
+                                void *rbuf, int rcount, struct ompi_datatype_t *rdtype,
+                                struct ompi_communicator_t *comm, struct ompi_info_t *info,
+                                ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    return rocm_alltoall_common(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, info, request,
+                                (mca_coll_rocm_module_t *) module, A2A_PERSISTENT);
+}
+
+int mca_coll_rocm_alltoallv_init(const void *sbuf, const int *scounts, const int *sdisps,
+                                 struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
+                                 const int *rdisps, struct ompi_datatype_t *rdtype,
+                                 struct ompi_communicator_t *comm, struct ompi_info_t *info,
+                                 ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    return rocm_alltoallv_common(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
+                                 info, request, (mca_coll_rocm_module_t *) module, A2A_PERSISTENT);
+}
+#endif /* ROCM_HAVE_ALLTOALL */
