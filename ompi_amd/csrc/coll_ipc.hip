@@ -76,6 +76,7 @@
 #include "comm_internal.h"
 #include "host_mark.h"
 #include "coll_kernels.h"
+#include "coll_landing.h"
 #include "ipc_registry.h"
 #include "op_device.h"
 #include "runtime.h"
@@ -87,11 +88,6 @@ namespace ompi_amd {
         int rc_ = (x);                           \
         if (rc_ != OMPI_AMD_SUCCESS) return rc_; \
     } while (0)
-
-// Largest allocation the library exports or maps: on ROCm 7.2
-// hipIpcOpenMemHandle of a 2 GiB + 2 MiB allocation never returned (four
-// ranks on one MI355X, OMPI_AMD_TRACE=1); 1 GiB opened in < 1 ms.
-constexpr size_t kMaxIpcBytes = (2ull << 30) - (4u << 20);
 
 // ---------------------------------------------------------------- barrier
 // A rank that fails a call its peers may already have launched (a deferred
@@ -1466,6 +1462,15 @@ static void land_desc(char *fresh, size_t want, buf_desc *d) {
     }
 }
 
+// Whether a call of `bytes` leaves the staged path; lands_lib: and nothing of
+// the caller's may be exported, so it stores through the landing buffers.
+static bool lands(const ompi_amd_comm_t *c, size_t bytes) {
+    return c->size > 1 && bytes > c->small_bytes && c->zero_copy;
+}
+static bool lands_lib(const ompi_amd_comm_t *c, size_t bytes) {
+    return lands(c, bytes) && !c->user_ipc && !c->force_shadow;
+}
+
 static int ensure_landing(ompi_amd_comm_t *c, size_t need) {
     if (need <= c->land_bytes) return OMPI_AMD_SUCCESS;
     constexpr size_t kTag = kLandTag;
@@ -2254,7 +2259,7 @@ static int allreduce_staged_two_shot(ompi_amd_comm_t *c, const void *src, void *
 }
 
 // sp / rp: every rank's input and rbuf as this rank maps them (sp = rp in
-// place); push needs rp only, and the landing buffer sized by push_slot.
+// place); push needs rp only, and the landing buffer sized by push_landing.
 static int allreduce_pull(ompi_amd_comm_t *c, const ptr_set &sp, const ptr_set &rp, void *rbuf,
                           int64_t count, int op, int type, const fold_plan &fp, hipStream_t s) {
     const int n = c->size, mine = (c->rank + 1) % n;
@@ -2330,20 +2335,14 @@ static int allreduce_pull_push(ompi_amd_comm_t *c, const ptr_set &sp, const ptr_
 }
 
 // slot r of the owner's landing buffer receives rank r's copy of the
-// owner's block, at the block's own phase mod 16 B
-static size_t push_slot(int64_t count, int n, int type) {
-    int64_t split, early, late;
-    blockcount(count, n, &split, &early, &late);
-    return ((size_t)(early * (int64_t)ompi_amd_type_extent(type)) + 16 + 255) & ~(size_t)255;
-}
-
+// owner's block, at the block's own phase mod 16 B (push_landing)
 static int allreduce_push(ompi_amd_comm_t *c, const void *src, const ptr_set &rp, int64_t count,
                           int op, int type, const fold_plan &fp, hipStream_t s) {
     const int n = c->size, mine = (c->rank + 1) % n;
     const int64_t ext = (int64_t)ompi_amd_type_extent(type);
     int64_t split, early, late;
     blockcount(count, n, &split, &early, &late);
-    const size_t slot = push_slot(count, n, type);
+    const size_t slot = push_landing(n, (size_t)count, (size_t)ext).slot;
     cp_jobs cj{};
     for (int b = 0; b < n; ++b) {
         if (b == mine) continue;
@@ -2438,20 +2437,22 @@ static bool pipe_fits(const ompi_amd_comm_t *c, const fold_plan &fp) {
 // of every peer's landing buffer instead), G gathers the other blocks from
 // the owners' result slots (push-land: from my own result slots).
 static int allreduce_push_pipe(ompi_amd_comm_t *c, const void *src, void *rbuf, int64_t count,
-                               int op, int type, const fold_plan &fp, hipStream_t s, bool land) {
+                               int op, int type, const fold_plan &fp, hipStream_t s,
+                               const land_layout &L) {
     const int n = c->size, mine = (c->rank + 1) % n;
     const int64_t ext = (int64_t)ompi_amd_type_extent(type);
     int64_t split, early, late;
     blockcount(count, n, &split, &early, &late);
-    const size_t slot = push_slot(count, n, type);
+    const size_t slot = L.slot, res = L.result_off;
+    const bool land = L.land;
     ptr_set dst_c{}, src_f{}, dst_f{}, src_g{};
     for (int b = 0; b < n; ++b) {
         if (b == mine) continue;
         const int owner = (b + n - 1) % n;
         const int64_t off = block_off(b, split, early, late) * ext;
         dst_c.p[b] = c->peer_land.p[owner] + (size_t)c->rank * slot + (off & 15) - off;
-        src_g.p[b] = land ? c->land + (size_t)(n + b) * slot + (off & 15) - off
-                          : c->peer_land.p[owner] + (size_t)n * slot + (off & 15) - off;
+        src_g.p[b] = land ? c->land + res + (size_t)b * slot + (off & 15) - off
+                          : c->peer_land.p[owner] + res + (off & 15) - off;
     }
     const int64_t offm = block_off(mine, split, early, late) * ext;
     for (int r = 0; r < n; ++r)
@@ -2461,11 +2462,11 @@ static int allreduce_push_pipe(ompi_amd_comm_t *c, const void *src, void *rbuf, 
     if (land) {
         for (int k = 1; k < n; ++k) {
             const int q = (c->rank + k) % n;
-            dst_f.p[k] = c->peer_land.p[q] + (size_t)(n + mine) * slot + (offm & 15) - offm;
+            dst_f.p[k] = c->peer_land.p[q] + res + (size_t)mine * slot + (offm & 15) - offm;
         }
         ndst = n;
     } else {
-        dst_f.p[1] = c->land + (size_t)n * slot + (offm & 15) - offm;
+        dst_f.p[1] = c->land + res + (offm & 15) - offm;
     }
     // the previous landing call's trailing barrier ended every reader of
     // these slots: no leading barrier
@@ -2499,15 +2500,9 @@ static int allreduce_pull_pipe(ompi_amd_comm_t *c, const ptr_set &sp, char *sh, 
     return launch_barrier(c, s);
 }
 
-// Landing bytes of the staged push schemes: push-gather needs n input slots
-// and its result slot [n]; push-land n input slots and n result slots (one
-// per block).  Push-land falls back to push-gather when its 2n slots would
-// pass the IPC size limit (every rank computes the same for the same count).
-static size_t staged_push_landing(int n, int algorithm, int64_t count, int type, bool *land) {
-    const size_t slot = push_slot(count, n, type);
-    const bool l = is_land(algorithm) && slot * (size_t)(2 * n) <= kMaxIpcBytes;
-    if (land) *land = l;
-    return slot * (size_t)(l ? 2 * n : n + 1);
+// the staged push schemes' landing layout for a communicator's algorithm
+static land_layout staged_push_layout(int n, int algorithm, size_t count, int type) {
+    return staged_push_landing(n, count, ompi_amd_type_extent(type), is_land(algorithm));
 }
 
 // The push scheme with a gather instead of remote result stores: nothing
@@ -2535,11 +2530,11 @@ static int allreduce_push_gather(ompi_amd_comm_t *c, const void *src, void *rbuf
     const int64_t ext = (int64_t)ompi_amd_type_extent(type);
     int64_t split, early, late;
     blockcount(count, n, &split, &early, &late);
-    const size_t slot = push_slot(count, n, type);
-    bool land = false;
-    TRY(ensure_landing(c, staged_push_landing(n, algorithm, count, type, &land)));
+    const land_layout L = staged_push_layout(n, algorithm, (size_t)count, type);
+    const size_t slot = L.slot, res = L.result_off;
+    TRY(ensure_landing(c, L.need));
     if (is_pipe(algorithm) && pipe_fits(c, fp))
-        return allreduce_push_pipe(c, src, rbuf, count, op, type, fp, s, land);
+        return allreduce_push_pipe(c, src, rbuf, count, op, type, fp, s, L);
     cp_jobs cj{};
     for (int b = 0; b < n; ++b) {
         if (b == mine) continue;
@@ -2562,10 +2557,10 @@ static int allreduce_push_gather(ompi_amd_comm_t *c, const void *src, void *rbuf
     fold_jobs(fp, count, n, mine, &jobs);
     ptr_set dsts{};
     dsts.p[0] = (const char *)rbuf;
-    if (land) {
+    if (L.land) {
         for (int k = 1; k < n; ++k) {
             const int q = (c->rank + k) % n;
-            dsts.p[k] = c->peer_land.p[q] + (size_t)(n + mine) * slot + (offm & 15) - offm;
+            dsts.p[k] = c->peer_land.p[q] + res + (size_t)mine * slot + (offm & 15) - offm;
         }
         TRY(timed_phase(c, 0, s, [&] {
             return launch_reduce(c, op, type, srcs, n, dsts, n, fp.order, fp.flags, jobs, s);
@@ -2575,13 +2570,13 @@ static int allreduce_push_gather(ompi_amd_comm_t *c, const void *src, void *rbuf
         for (int b = 0; b < n; ++b) {
             if (b == mine) continue;
             const int64_t off = block_off(b, split, early, late) * ext;
-            cj.j[cj.n++] = {c->land + (size_t)(n + b) * slot + (off & 15), (char *)rbuf + off,
+            cj.j[cj.n++] = {c->land + res + (size_t)b * slot + (off & 15), (char *)rbuf + off,
                             block_cnt(b, split, early, late) * ext};
         }
         TRY(timed_phase(c, 1, s, [&] { return launch_copy(c, cj, s); }));
         return launch_barrier(c, s);
     }
-    dsts.p[1] = c->land + (size_t)n * slot + (offm & 15) - offm;
+    dsts.p[1] = c->land + res + (offm & 15) - offm;
     TRY(timed_phase(c, 0, s, [&] {
         return launch_reduce(c, op, type, srcs, n, dsts, 2, fp.order, fp.flags, jobs, s);
     }));
@@ -2591,8 +2586,8 @@ static int allreduce_push_gather(ompi_amd_comm_t *c, const void *src, void *rbuf
         if (b == mine) continue;
         const int owner = (b + n - 1) % n;
         const int64_t off = block_off(b, split, early, late) * ext;
-        const char *res = c->peer_land.p[owner] + (size_t)n * slot + (off & 15);
-        cj.j[cj.n++] = {res, (char *)rbuf + off, block_cnt(b, split, early, late) * ext};
+        cj.j[cj.n++] = {c->peer_land.p[owner] + res + (off & 15), (char *)rbuf + off,
+                        block_cnt(b, split, early, late) * ext};
     }
     TRY(timed_phase(c, 1, s, [&] { return launch_copy(c, cj, s); }));
     return launch_barrier(c, s);
@@ -2616,20 +2611,21 @@ static int reduce_my_block(ompi_amd_comm_t *c, const void *src, void *rbuf, size
     jobs.j[0] = {off, cnt, 0, ro.first, -1};
     const int n = c->size;
     const size_t ext = ompi_amd_type_extent(type);
-    if (total_bytes <= c->small_bytes || !c->zero_copy) {
+    if (!lands(c, total_bytes)) {
         stage_half sh;
         TRY(stage_in(c, src, total_bytes, &sh, s));
         return launch_reduce(c, op, type, sh.peers, n, one_ptr(rbuf), 1, ro.order, ro.flags, jobs, s);
     }
-    if (!c->pre && !c->user_ipc && !c->force_shadow) {
+    if (!c->pre && lands_lib(c, total_bytes)) {
         // Staged push (nothing of the caller's exported, no staging copy):
         // block b of my input into slot [me] of rank b's landing buffer
         // (at its own phase mod 16), barrier, fold my block from my input
         // and my landing slots, barrier (peers then may reuse the slots).
         // In place, the result goes through landing slot [n] (it may
         // overlap my own block of the input, reduce_scatter's uneven counts).
-        const size_t slot = ((size_t)max_cnt * ext + 16 + 255) & ~(size_t)255;
-        TRY(ensure_landing(c, slot * (size_t)(n + 1)));
+        const land_layout L = reduce_scatter_landing(n, (size_t)max_cnt, ext);
+        const size_t slot = L.slot;
+        TRY(ensure_landing(c, L.need));
         cp_jobs cj{};
         int64_t ob = 0;
         for (int b = 0; b < n; ++b) {
@@ -2650,7 +2646,7 @@ static int reduce_my_block(ompi_amd_comm_t *c, const void *src, void *rbuf, size
         for (int r = 0; r < n; ++r)
             srcs.p[r] = (r == c->rank) ? (const char *)src
                                        : c->land + (size_t)r * slot + (offb & 15) - offb;
-        char *res = inplace ? c->land + (size_t)n * slot + (offb & 15) : (char *)rbuf;
+        char *res = inplace ? c->land + L.result_off + (offb & 15) : (char *)rbuf;
         jobs.j[0].off_dst = 0;
         if (cnt > 0)
             TRY(launch_reduce(c, op, type, srcs, n, one_ptr(res), 1, ro.order, ro.flags, jobs, s));
@@ -2673,7 +2669,7 @@ static int reduce_my_block(ompi_amd_comm_t *c, const void *src, void *rbuf, size
     bool any_inplace = false;
     for (int p = 0; p < n; ++p) any_inplace = any_inplace || (fl[p] & 1);
     if (any_inplace)  // collective: every rank sees the same flags and max_cnt
-        TRY(ensure_landing(c, (size_t)max_cnt * ext + 256));
+        TRY(ensure_landing(c, reduce_scatter_inplace_landing((size_t)max_cnt, ext).need));
     TRY(launch_barrier(c, s));
     void *dst = inplace ? (void *)c->land : rbuf;
     TRY(launch_reduce(c, op, type, sp, n, one_ptr(dst), 1, ro.order, ro.flags, jobs, s));
@@ -2745,14 +2741,14 @@ static int scan_common(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
         if (exclusive || inplace) return OMPI_AMD_SUCCESS;
         return record_hip(hipMemcpyAsync(rbuf, src, bytes, hipMemcpyDeviceToDevice, s), "copy");
     }
-    if (bytes <= c->small_bytes || !c->zero_copy) {
+    if (!lands(c, bytes)) {
         stage_half sh;
         TRY(stage_in(c, src, bytes, &sh, s));
         return launch_reduce(c, op, type, sh.peers, nsrc, one_ptr(rbuf), 1, ORDER_RING, 0, jobs, s);
     }
     // large: inputs go through the landing buffers (a peer may still read
     // my input while I write my result in place), then one fold per rank
-    TRY(ensure_landing(c, bytes + 256));
+    TRY(ensure_landing(c, scan_landing(bytes).need));
     cp_jobs cj{};
     cj.n = 1;
     cj.j[0] = {(const char *)src, c->land, (int64_t)bytes};
@@ -3204,7 +3200,7 @@ static int allreduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size
     TRY(shadow_in(c, sh, s));
     int rc;
     if (push) {
-        TRY(ensure_landing(c, push_slot((int64_t)count, n, type) * (size_t)n));
+        TRY(ensure_landing(c, push_landing(n, count, ext).need));
         TRY(exchange_bufs(c, nullptr, rbuf, &sp, &rp));
         rc = allreduce_push(c, src, rp, (int64_t)count, op, type, fp, s);
     } else {
@@ -3766,87 +3762,7 @@ int ompi_amd_allreduce(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
     return rc;
 }
 
-int ompi_amd_iallreduce(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,
-                        int op, void *stream, ompi_amd_request_t **out) {
-    api_guard api_(c);
-    if (!c || !rbuf || !out) return OMPI_AMD_ERR_BAD_PARAM;
-    *out = nullptr;
-    if (!ompi_amd_op_supported(op, type)) return OMPI_AMD_ERR_UNSUPPORTED;
-    TRY(check_sticky(c));
-    TRY(set_dev(c));
-    auto *req = new (std::nothrow) ompi_amd_request;
-    if (!req) return OMPI_AMD_ERR_BAD_PARAM;
-    req->c = c;
-    req->mark = mark_word_get();
-    int rc = record_hip(req_event_get(c, &req->ev), "request event");
-    if (rc != OMPI_AMD_SUCCESS) {
-        delete req;
-        return rc;
-    }
-    path_params pp = params_of(c);
-    nb_tuned(c, &pp, count, type);
-    const bool inplace = in_place(sbuf, rbuf);
-    if (pp.tuned_alg == TUNED_AR_NONOVERLAPPING) {  // a host exchange, in order with the others
-        rc = drain(c);
-        if (rc == OMPI_AMD_SUCCESS) rc = agree_root0_inplace(c, &pp, inplace);
-        if (rc != OMPI_AMD_SUCCESS) {
-            req_event_put(req->c, req->ev);
-            delete req;
-            return rc;
-        }
-    }
-    pending_op o{0, inplace ? rbuf : sbuf, rbuf, count, type, op, comm_stream(c, stream), pp, req};
-    if (allreduce_push_gathers(c, pp, count, type)) {
-        // no swap: only the landing buffer must be big enough at the launch
-        // (a growth queued ahead of this call: nb_grow)
-        rc = nb_grow(c, staged_push_landing(c->size, pp.algorithm, (int64_t)count, type, nullptr), o.stream);
-        if (rc != OMPI_AMD_SUCCESS) {
-            req_event_put(req->c, req->ev);
-            delete req;
-            return rc;
-        }
-    } else if (allreduce_swaps(c, pp, count, type)) {
-        // post this rank's half of the handle swap now; the launch waits for
-        // the peers' halves (progress / the next collective call)
-        const bool push = is_push(pp.algorithm);
-        if (push) rc = nb_grow(c, push_slot((int64_t)count, c->size, type) * (size_t)c->size, o.stream);
-        // export fallback with memory of its own (several calls may be
-        // outstanding): the posted descriptors are the shadows'
-        const size_t bytes = count * ompi_amd_type_extent(type);
-        if (rc == OMPI_AMD_SUCCESS) {
-            const void *xs = push ? nullptr : o.sbuf;
-            void *xr = o.rbuf;
-            rc = push ? shadow_plan(c, &xs, 0, &xr, bytes, false, true, &o.sh)
-                      : shadow_plan(c, &xs, bytes, &xr, bytes, inplace, true, &o.sh);
-            if (!push) o.sbuf = xs;
-            o.rbuf = xr;
-            req->shadow = o.sh.mem;
-            req->shadow2 = o.sh.mem2;
-        }
-        call_blob mine{};
-        if (rc == OMPI_AMD_SUCCESS && !push) rc = export_buf(c, o.sbuf, &mine.s);
-        if (rc == OMPI_AMD_SUCCESS) rc = export_buf(c, o.rbuf, &mine.r);
-        if (rc == OMPI_AMD_SUCCESS) rc = nb_ticket(c, o, &mine, sizeof(mine));
-        if (rc != OMPI_AMD_SUCCESS) {
-            req_event_put(req->c, req->ev);
-            arena_free(c, req->shadow);
-            arena_free(c, req->shadow2);
-            delete req;
-            return rc;
-        }
-    }
-    c->pending.push_back(o);
-    c->npending.fetch_add(1);
-    *out = req;
-    return post_progress(c);
-}
-
-// ---- nonblocking reduce_scatter_block / allgather / bcast ----
-// The iallreduce machinery (post now, launch from progress in posting
-// order): a staged size is enqueued at once; a zero-copy size posts this
-// rank's descriptor of what peers read (`exp`, `bytes`; an owned shadow
-// when the runtime refuses the export, or when `force` asks for one) and
-// launches once every peer has posted.
+// ---- a nonblocking call's request: begin, abandon (a failed post), enqueue ----
 static int nb_begin(ompi_amd_comm_t *c, ompi_amd_request **out) {
     *out = nullptr;
     TRY(check_sticky(c));
@@ -3864,6 +3780,91 @@ static int nb_begin(ompi_amd_comm_t *c, ompi_amd_request **out) {
     return OMPI_AMD_SUCCESS;
 }
 
+// the post failed: release the request and the shadows it owns (null where
+// none was made)
+static void nb_abandon(ompi_amd_comm_t *c, ompi_amd_request *req) {
+    req_event_put(c, req->ev);
+    arena_free(c, req->shadow);
+    arena_free(c, req->shadow2);
+    delete req;
+}
+
+static int nb_enqueue(ompi_amd_comm_t *c, const pending_op &o, ompi_amd_request_t **out) {
+    c->pending.push_back(o);
+    c->npending.fetch_add(1);
+    *out = o.req;
+    return post_progress(c);
+}
+
+// A deferred call's landing buffer, sized at post time for its launch: the
+// growth is queued ahead of the call (nb_grow; every rank posts the same
+// call alike); on failure the request is released.
+static int nb_grow_landing(ompi_amd_comm_t *c, size_t need, ompi_amd_request *req, hipStream_t s) {
+    const int rc = nb_grow(c, need, s);
+    if (rc != OMPI_AMD_SUCCESS) nb_abandon(c, req);
+    return rc;
+}
+
+int ompi_amd_iallreduce(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,
+                        int op, void *stream, ompi_amd_request_t **out) {
+    api_guard api_(c);
+    if (!c || !rbuf || !out) return OMPI_AMD_ERR_BAD_PARAM;
+    *out = nullptr;
+    if (!ompi_amd_op_supported(op, type)) return OMPI_AMD_ERR_UNSUPPORTED;
+    ompi_amd_request *req = nullptr;
+    TRY(nb_begin(c, &req));
+    int rc = OMPI_AMD_SUCCESS;
+    path_params pp = params_of(c);
+    nb_tuned(c, &pp, count, type);
+    const bool inplace = in_place(sbuf, rbuf);
+    if (pp.tuned_alg == TUNED_AR_NONOVERLAPPING) {  // a host exchange, in order with the others
+        rc = drain(c);
+        if (rc == OMPI_AMD_SUCCESS) rc = agree_root0_inplace(c, &pp, inplace);
+        if (rc != OMPI_AMD_SUCCESS) {
+            nb_abandon(c, req);
+            return rc;
+        }
+    }
+    pending_op o{0, inplace ? rbuf : sbuf, rbuf, count, type, op, comm_stream(c, stream), pp, req};
+    if (allreduce_push_gathers(c, pp, count, type)) {
+        // no swap: only the landing buffer must be big enough at the launch
+        TRY(nb_grow_landing(c, staged_push_layout(c->size, pp.algorithm, count, type).need, req, o.stream));
+    } else if (allreduce_swaps(c, pp, count, type)) {
+        // post this rank's half of the handle swap now; the launch waits for
+        // the peers' halves (progress / the next collective call)
+        const bool push = is_push(pp.algorithm);
+        const size_t bytes = count * ompi_amd_type_extent(type);
+        if (push) rc = nb_grow(c, push_landing(c->size, count, ompi_amd_type_extent(type)).need, o.stream);
+        // export fallback with memory of its own (several calls may be
+        // outstanding): the posted descriptors are the shadows'
+        if (rc == OMPI_AMD_SUCCESS) {
+            const void *xs = push ? nullptr : o.sbuf;
+            void *xr = o.rbuf;
+            rc = push ? shadow_plan(c, &xs, 0, &xr, bytes, false, true, &o.sh)
+                      : shadow_plan(c, &xs, bytes, &xr, bytes, inplace, true, &o.sh);
+            if (!push) o.sbuf = xs;
+            o.rbuf = xr;
+            req->shadow = o.sh.mem;
+            req->shadow2 = o.sh.mem2;
+        }
+        call_blob mine{};
+        if (rc == OMPI_AMD_SUCCESS && !push) rc = export_buf(c, o.sbuf, &mine.s);
+        if (rc == OMPI_AMD_SUCCESS) rc = export_buf(c, o.rbuf, &mine.r);
+        if (rc == OMPI_AMD_SUCCESS) rc = nb_ticket(c, o, &mine, sizeof(mine));
+        if (rc != OMPI_AMD_SUCCESS) {
+            nb_abandon(c, req);
+            return rc;
+        }
+    }
+    return nb_enqueue(c, o, out);
+}
+
+// ---- nonblocking reduce_scatter_block / allgather / bcast ----
+// The iallreduce machinery (post now, launch from progress in posting
+// order): a staged size is enqueued at once; a zero-copy size posts this
+// rank's descriptor of what peers read (`exp`, `bytes`; an owned shadow
+// when the runtime refuses the export, or when `force` asks for one) and
+// launches once every peer has posted.
 static int nb_post(ompi_amd_comm_t *c, pending_op &o, const void **exp, size_t bytes, bool force,
                    ompi_amd_request_t **out) {
     int rc = OMPI_AMD_SUCCESS;
@@ -3881,32 +3882,10 @@ static int nb_post(ompi_amd_comm_t *c, pending_op &o, const void **exp, size_t b
         if (rc == OMPI_AMD_SUCCESS) rc = nb_ticket(c, o, &mine, sizeof(mine));
     }
     if (rc != OMPI_AMD_SUCCESS) {
-        req_event_put(req->c, req->ev);
-        arena_free(c, req->shadow);
-        arena_free(c, req->shadow2);
-        delete req;
+        nb_abandon(c, req);
         return rc;
     }
-    c->pending.push_back(o);
-    c->npending.fetch_add(1);
-    *out = req;
-    return post_progress(c);
-}
-
-static bool nb_swaps(const ompi_amd_comm_t *c, size_t bytes) {
-    return c->size > 1 && bytes > 0 && bytes > c->small_bytes && c->zero_copy;
-}
-
-// A deferred call's landing buffer grown at post time (growth is collective
-// and blocking: every rank posts the same call alike); on failure the
-// request is released.
-static int nb_grow_landing(ompi_amd_comm_t *c, size_t need, ompi_amd_request *req, hipStream_t s) {
-    const int rc = nb_grow(c, need, s);
-    if (rc != OMPI_AMD_SUCCESS) {
-        req_event_put(req->c, req->ev);
-        delete req;
-    }
-    return rc;
+    return nb_enqueue(c, o, out);
 }
 
 int ompi_amd_ireduce_scatter_block(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t rcount,
@@ -3921,13 +3900,13 @@ int ompi_amd_ireduce_scatter_block(ompi_amd_comm_t *c, const void *sbuf, void *r
     const size_t total = rcount * (size_t)c->size * ompi_amd_type_extent(type);
     pending_op o{0, inplace ? rbuf : sbuf, rbuf, rcount, type, op, comm_stream(c, stream), params_of(c), req};
     o.kind = PEND_RSB;
-    const bool swap = nb_swaps(c, total);
-    if (swap && !c->user_ipc && !c->force_shadow) {
+    const bool swap = lands(c, total);
+    if (lands_lib(c, total)) {
         // staged push (reduce_my_block): no swap, so no host rendezvous at
         // launch; only the landing buffer must be big enough beforehand
         // (its growth is collective: every rank posts this call alike)
-        const size_t slot = (rcount * ompi_amd_type_extent(type) + 16 + 255) & ~(size_t)255;
-        TRY(nb_grow_landing(c, slot * (size_t)(c->size + 1), req, o.stream));
+        TRY(nb_grow_landing(c, reduce_scatter_landing(c->size, rcount, ompi_amd_type_extent(type)).need, req,
+                            o.stream));
         o.inplace = inplace;
         return nb_post(c, o, nullptr, 0, false, out);
     }
@@ -3950,7 +3929,7 @@ int ompi_amd_iallgather(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t
     o.kind = PEND_ALLGATHER;
     // in place: keep the (void *)1 spelling unless peers read a shadow
     if (inplace) o.sbuf = (const void *)1;
-    if (!nb_swaps(c, bytes)) return nb_post(c, o, nullptr, 0, false, out);
+    if (!lands(c, bytes)) return nb_post(c, o, nullptr, 0, false, out);
     if (const size_t need = ag_landing_need(c, bytes)) {
         TRY(nb_grow_landing(c, need, req, o.stream));
         o.land = true;  // stores into the peers' landing buffers: nothing to post
@@ -3970,16 +3949,13 @@ int ompi_amd_ibcast(ompi_amd_comm_t *c, void *buf, size_t bytes, int root, void 
     pending_op o{0, buf, buf, bytes, 0, 0, comm_stream(c, stream), params_of(c), req};
     o.kind = PEND_BCAST;
     o.root = root;
-    if (nb_swaps(c, bytes)) {
-        if (const size_t need = bcast_landing_need(c, bytes)) {
-            TRY(nb_grow_landing(c, need, req, o.stream));
-            o.land = true;  // stores into the peers' landing buffers: nothing to post
-            return nb_post(c, o, nullptr, 0, false, out);
-        }
+    if (!lands(c, bytes)) return nb_post(c, o, nullptr, 0, false, out);
+    if (const size_t need = bcast_landing_need(c, bytes)) {
+        TRY(nb_grow_landing(c, need, req, o.stream));
+        o.land = true;  // stores into the peers' landing buffers: nothing to post
+        return nb_post(c, o, nullptr, 0, false, out);
     }
-    if (!nb_swaps(c, bytes) || c->rank != root) {
-        // non-roots export nothing, but post their (empty) half all the same
-        if (!nb_swaps(c, bytes)) return nb_post(c, o, nullptr, 0, false, out);
+    if (c->rank != root) {  // non-roots export nothing, but post their (empty) half all the same
         const void *nothing = nullptr;
         return nb_post(c, o, &nothing, 0, false, out);
     }
@@ -4009,25 +3985,17 @@ int ompi_amd_ireduce(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t co
     pending_op o{0, sbuf, rbuf, count, type, op, comm_stream(c, stream), params_of(c), req};
     o.kind = PEND_REDUCE;
     o.root = root;
-    if (n > 1 && count > 0 && bytes > c->small_bytes && c->zero_copy) {
-        int64_t split, early, late;
-        blockcount((int64_t)count, n, &split, &early, &late);
-        const size_t slot = ((size_t)early * ompi_amd_type_extent(type) + 16 + 255) & ~(size_t)255;
-        TRY(nb_grow_landing(c, slot * (size_t)n + ((bytes + 255) & ~(size_t)255), req, o.stream));
-    }
+    if (lands(c, bytes))  // progress launches it with user_ipc / force_shadow off: reduce_impl's staged push
+        TRY(nb_grow_landing(c, reduce_landing(n, count, ompi_amd_type_extent(type)).need, req, o.stream));
     if (n == 1 || count == 0) return nb_post(c, o, nullptr, 0, false, out);
     call_blob mine{};
     mine.flags = (c->rank == root && in_place(sbuf, rbuf)) ? 1 : 0;
     const int rc = nb_ticket(c, o, &mine, sizeof(mine));
     if (rc != OMPI_AMD_SUCCESS) {
-        req_event_put(req->c, req->ev);
-        delete req;
+        nb_abandon(c, req);
         return rc;
     }
-    c->pending.push_back(o);
-    c->npending.fetch_add(1);
-    *out = req;
-    return post_progress(c);
+    return nb_enqueue(c, o, out);
 }
 
 static int iscan_common(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,
@@ -4041,8 +4009,7 @@ static int iscan_common(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t
     pending_op o{0, sbuf, rbuf, count, type, op, comm_stream(c, stream), params_of(c), req};
     o.kind = PEND_SCAN;
     o.exclusive = exclusive;
-    if (c->size > 1 && count > 0 && bytes > c->small_bytes && c->zero_copy)
-        TRY(nb_grow_landing(c, bytes + 256, req, o.stream));
+    if (lands(c, bytes)) TRY(nb_grow_landing(c, scan_landing(bytes).need, req, o.stream));
     return nb_post(c, o, nullptr, 0, false, out);
 }
 
@@ -4076,10 +4043,8 @@ int ompi_amd_ireduce_scatter(ompi_amd_comm_t *c, const void *sbuf, void *rbuf,
         total += v;
         maxc = std::max(maxc, v);
     }
-    if (c->size > 1 && total * ext > c->small_bytes && c->zero_copy) {  // reduce_my_block's staged push
-        const size_t slot = (maxc * ext + 16 + 255) & ~(size_t)255;
-        TRY(nb_grow_landing(c, slot * (size_t)(c->size + 1), req, o.stream));
-    }
+    if (lands(c, total * ext))  // reduce_my_block's staged push
+        TRY(nb_grow_landing(c, reduce_scatter_landing(c->size, maxc, ext).need, req, o.stream));
     return nb_post(c, o, nullptr, 0, false, out);
 }
 
@@ -4118,7 +4083,7 @@ static int reduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
     const red_order ro = tuned_reduce_order(n, type_size(type) * count, count, root, root_inplace_all,
                                             c->tuned_red_alg);
     red_jobs jobs;
-    if (bytes <= c->small_bytes || !c->zero_copy) {
+    if (!lands(c, bytes)) {
         // staged: everyone stages, the root folds everything
         stage_half sh;
         TRY(stage_in(c, src, bytes, &sh, s));
@@ -4129,7 +4094,7 @@ static int reduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
     }
     int64_t split, early, late;
     blockcount((int64_t)count, n, &split, &early, &late);
-    if (!c->user_ipc && !c->force_shadow) {
+    if (lands_lib(c, bytes)) {
         // Staged push (nothing of the caller's exported, no staging copy on
         // the non-roots): block b of my input into slot [me] of rank b's
         // landing buffer, barrier, rank b folds block b locally and stores
@@ -4137,9 +4102,9 @@ static int reduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
         // the result into rbuf, barrier (the next landing call's scatter
         // may land where this result area was).
         const int64_t ext = (int64_t)ompi_amd_type_extent(type);
-        const size_t slot = ((size_t)early * (size_t)ext + 16 + 255) & ~(size_t)255;
-        const size_t res_off = slot * (size_t)n;
-        TRY(ensure_landing(c, res_off + ((bytes + 255) & ~(size_t)255)));
+        const land_layout L = reduce_landing(n, count, (size_t)ext);
+        const size_t slot = L.slot, res_off = L.result_off;
+        TRY(ensure_landing(c, L.need));
         cp_jobs cj{};
         for (int b = 0; b < n; ++b) {
             const int64_t off = block_off(b, split, early, late) * ext, cb = block_cnt(b, split, early, late);
@@ -4413,7 +4378,7 @@ static int bcast_impl(ompi_amd_comm_t *c, void *buf, const void *root_src, size_
         }
         if (every) {
             const int n = c->size;
-            const size_t blk = ((bytes + (size_t)n - 1) / (size_t)n + 255) & ~(size_t)255;
+            const size_t blk = bcast_block(n, bytes);
             auto block = [&](int b, size_t *off, size_t *len) {
                 *off = std::min(bytes, (size_t)b * blk);
                 *len = std::min(bytes, *off + blk) - *off;
@@ -4468,22 +4433,15 @@ static int bcast_impl(ompi_amd_comm_t *c, void *buf, const void *root_src, size_
 // is 16-B aligned (the copies stay 16-B vectors for aligned buffers).
 // Every landing call ends with a barrier (the next landing call of any
 // collective may store into these bytes without a leading one).
-static size_t ag_land_slot(size_t bytes) { return (bytes + 16 + 255) & ~(size_t)255; }
 
 // Landing bytes a deferred allgather (bcast) needs, or 0 when it does not
 // take the landing path (user_ipc / force_shadow, a staged size, or past
 // the IPC size limit); every rank computes the same for the same call.
 static size_t ag_landing_need(const ompi_amd_comm_t *c, size_t bytes) {
-    if (c->user_ipc || c->force_shadow || c->size == 1 || bytes <= c->small_bytes || !c->zero_copy)
-        return 0;
-    const size_t need = ag_land_slot(bytes) * (size_t)c->size;
-    return need + (64u << 20) <= kMaxIpcBytes ? need : 0;
+    return lands_lib(c, bytes) ? allgather_landing(c->size, bytes).need : 0;
 }
 static size_t bcast_landing_need(const ompi_amd_comm_t *c, size_t bytes) {
-    if (c->user_ipc || c->force_shadow || c->size == 1 || bytes <= c->small_bytes || !c->zero_copy)
-        return 0;
-    const size_t need = ((bytes + 255) & ~(size_t)255) + 256;
-    return need + (64u << 20) <= kMaxIpcBytes ? need : 0;
+    return lands_lib(c, bytes) ? bcast_landing(c->size, bytes).need : 0;
 }
 
 // Store my block into slot [me] of every peer's landing buffer (local rbuf
@@ -4496,8 +4454,11 @@ static int allgather_land(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size
     if (bytes == 0) return OMPI_AMD_SUCCESS;
     TRY(set_dev(c));
     const int n = c->size;
-    const size_t slot = ag_land_slot(bytes);
-    TRY(ensure_landing(c, slot * (size_t)n));  // grown at post time: a no-op here
+    const land_layout L = allgather_landing(n, bytes);
+    const size_t slot = L.slot;
+    // the n slots (== L.need: the callers checked ag_landing_need); grown at
+    // post time for a deferred call: a no-op here
+    TRY(ensure_landing(c, L.result_off));
     ++c->land_ag_bcast;
     char *my_slot = (char *)rbuf + (size_t)c->rank * bytes;
     const bool inplace = sbuf == (const void *)1 || sbuf == (const void *)my_slot;
@@ -4534,9 +4495,10 @@ static int bcast_land(ompi_amd_comm_t *c, void *buf, size_t bytes, int root, hip
     if (bytes == 0 || c->size == 1) return OMPI_AMD_SUCCESS;
     TRY(set_dev(c));
     const int n = c->size, me = c->rank;
-    TRY(ensure_landing(c, ((bytes + 255) & ~(size_t)255) + 256));
+    const land_layout L = bcast_landing(n, bytes);
+    TRY(ensure_landing(c, L.result_off));  // == L.need: the callers checked bcast_landing_need
     ++c->land_ag_bcast;
-    const size_t blk = ((bytes + (size_t)n - 1) / (size_t)n + 255) & ~(size_t)255;
+    const size_t blk = L.blk;
     auto block = [&](int b, size_t *off, size_t *len) {
         *off = std::min(bytes, (size_t)b * blk);
         *len = std::min(bytes, *off + blk) - *off;
@@ -4605,7 +4567,7 @@ constexpr size_t kA2avNbChunk = 1u << 20;  // landing bytes per pair an ialltoal
 static size_t a2a_chunk_of(const ompi_amd_comm_t *c) {
     if (c->alltoall_chunk) return c->alltoall_chunk;
     // N slots of ag_land_slot(chunk) under ag_landing_need's cap
-    return ((kMaxIpcBytes - (64u << 20)) / (size_t)std::max(1, c->size) / 256 - 1) * 256;
+    return alltoall_fit_chunk(std::max(1, c->size), kMaxIpcBytes - kLandCapMargin);
 }
 
 static int a2a_path(const ompi_amd_comm_t *c, const path_params &pp, size_t M) {
@@ -4734,23 +4696,23 @@ static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, 
 
 static int alltoall_land(ompi_amd_comm_t *c, const a2a_call &k, size_t M, size_t chunk, bool may_grow,
                          hipStream_t s) {
-    const size_t n = (size_t)c->size;
     chunk = std::min(chunk, M);
-    if (n * ag_land_slot(chunk) > c->land_bytes) {
+    const size_t need = alltoall_landing(c->size, chunk, M).need;
+    if (need > c->land_bytes) {
         if (may_grow) {  // collective: every rank computes the same need
-            TRY(ensure_landing(c, n * ag_land_slot(chunk)));
+            TRY(ensure_landing(c, need));
         } else {
             // a deferred call runs in passes the landing buffer it finds can
             // hold (the same on every rank: growths switch at one queue position)
-            const size_t per = (c->land_bytes / n) & ~(size_t)255;
-            if (per < 512) {
+            const size_t fit = alltoall_fit_chunk(c->size, c->land_bytes);
+            if (!fit) {
                 record_msg("alltoall: no landing buffer for a deferred call (%zu B)", c->land_bytes);
                 return OMPI_AMD_ERR_UNSUPPORTED;
             }
-            chunk = std::min(chunk, per - 256);
+            chunk = std::min(chunk, fit);
         }
     }
-    const size_t slot = ag_land_slot(chunk);
+    const size_t slot = alltoall_landing(c->size, chunk, M).slot;
     for (size_t off = 0; off < M; off += chunk) {
         TRY(alltoall_exchange(c, k, off, chunk, c->land, c->peer_land, slot, true, s));
         ++c->alltoall_passes;
@@ -4862,22 +4824,18 @@ static int ia2a_post(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree
     if (n == 1) agree = false;
     o.a2a_M = agree ? 0 : M;
     size_t need = 0;
-    if (agree) need = n * ag_land_slot(std::min(o.a2a_chunk, kA2avNbChunk));
-    else if (a2a_path(c, o.pp, M) == A2A_LAND) need = n * ag_land_slot(std::min(o.a2a_chunk, M));
+    if (agree) need = alltoall_landing(c->size, o.a2a_chunk, kA2avNbChunk).need;
+    else if (a2a_path(c, o.pp, M) == A2A_LAND) need = alltoall_landing(c->size, o.a2a_chunk, M).need;
     if (need) TRY(nb_grow_landing(c, need, req, o.stream));
     if (!agree) return nb_post(c, o, nullptr, 0, false, out);
     call_blob mine{};
     mine.flags = (uint64_t)M;
     const int rc = nb_ticket(c, o, &mine, sizeof(mine));
     if (rc != OMPI_AMD_SUCCESS) {
-        req_event_put(req->c, req->ev);
-        delete req;
+        nb_abandon(c, req);
         return rc;
     }
-    c->pending.push_back(o);
-    c->npending.fetch_add(1);
-    *out = req;
-    return post_progress(c);
+    return nb_enqueue(c, o, out);
 }
 
 int ompi_amd_ialltoall(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, void *stream,
@@ -4933,11 +4891,11 @@ int ompi_amd_allreduce_init(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, si
     const bool push_gather = allreduce_push_gathers(c, pl->pp, count, type);
     const bool small = n == 1 || count == 0 || !allreduce_swaps(c, pl->pp, count, type) || push_gather;
     if (rc == OMPI_AMD_SUCCESS && push_gather)
-        rc = ensure_landing(c, staged_push_landing(n, pl->pp.algorithm, (int64_t)count, type, nullptr));
+        rc = ensure_landing(c, staged_push_layout(n, pl->pp.algorithm, count, type).need);
     pl->fp = allreduce_fold(n, pl->pp.tuned_alg, count, type, pl->pp.root0_inplace != 0, pl->pp.red_alg);
     if (!small) {
         pl->kind = is_push(c->algorithm) ? 3 : c->algorithm == ALG_PULL_PUSH ? 2 : 1;
-        if (pl->kind == 3) rc = ensure_landing(c, push_slot(pl->count, n, type) * (size_t)n);
+        if (pl->kind == 3) rc = ensure_landing(c, push_landing(n, count, ompi_amd_type_extent(type)).need);
         if (rc == OMPI_AMD_SUCCESS) {  // export fallback: shadows of the plan's own
             const void *xs = pl->kind == 3 ? nullptr : pl->src;
             void *xr = pl->rbuf;
@@ -5166,6 +5124,15 @@ int ompi_amd_plan_start(ompi_amd_plan_t *pl, void *stream) {
     return OMPI_AMD_SUCCESS;
 }
 
+// the start's completion event and mark, recorded at its first test / wait
+static int plan_record(ompi_amd_plan_t *pl) {
+    if (pl->recorded) return OMPI_AMD_SUCCESS;
+    TRY(record_hip(hipEventRecord(pl->done, pl->stream), "plan completion event"));
+    pl->mark_seq = mark_launch(pl->mark, pl->stream);
+    pl->recorded = true;
+    return OMPI_AMD_SUCCESS;
+}
+
 int ompi_amd_plan_test(ompi_amd_plan_t *pl, int *done) {
     api_guard api_(pl ? pl->c : nullptr);
     if (!pl || !done) return OMPI_AMD_ERR_BAD_PARAM;
@@ -5182,11 +5149,7 @@ int ompi_amd_plan_test(ompi_amd_plan_t *pl, int *done) {
         *done = 0;
         return OMPI_AMD_SUCCESS;
     }
-    if (!pl->recorded) {
-        TRY(record_hip(hipEventRecord(pl->done, pl->stream), "plan completion event"));
-        pl->mark_seq = mark_launch(pl->mark, pl->stream);
-        pl->recorded = true;
-    }
+    TRY(plan_record(pl));
     if (mark_seen(pl->mark, pl->mark_seq)) return check_sticky(pl->c);
     const hipError_t e = hipEventQuery(pl->done);
     if (e == hipErrorNotReady) {
@@ -5206,11 +5169,7 @@ int ompi_amd_plan_wait(ompi_amd_plan_t *pl) {
         TRY(record_hip(mark_value_wait(pl->stream, pl->mark, pl->embedded, progress_others), "plan wait"));
         return check_sticky(pl->c);
     }
-    if (!pl->recorded) {
-        TRY(record_hip(hipEventRecord(pl->done, pl->stream), "plan completion event"));
-        pl->mark_seq = mark_launch(pl->mark, pl->stream);
-        pl->recorded = true;
-    }
+    TRY(plan_record(pl));
     TRY(record_hip(wait_marked(pl->done, pl->mark, pl->mark_seq), "plan wait"));
     return check_sticky(pl->c);
 }

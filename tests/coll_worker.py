@@ -958,6 +958,120 @@ def case_cross_comm_grow(comm, rank, n, salt, nring=12):
     return not msgs, "; ".join(msgs[:3])
 
 
+LAND_STEP = (32 << 20) - 64  # usable bytes of a landing buffer's first 32 MiB step
+
+
+def case_nb_landing_sized_at_post(comm, rank, n, salt):
+    """The landing buffer grows in 32 MiB steps, so only a call whose need
+    sits at a step boundary shows a post / launch sizing mismatch.  For
+    reduce (root in place), reduce_scatter_block, reduce_scatter (uneven, one
+    empty block), scan and allgather: the largest count whose landing need
+    (the layouts of DESIGN.md §2.1, written out here) is <= 32 MiB - 64, run
+    nonblocking on one fresh communicator and blocking on another (allgather:
+    nonblocking only, its blocking form does not land).  Results exact, both
+    landing buffers exactly one step, one deferred growth on the nonblocking
+    communicator (its launch grew nothing)."""
+    F, SUM = mop.MPI_FLOAT, mop.MPI_SUM
+    ext = F.extent
+
+    def r256(x):
+        return (x + 255) & ~255
+
+    def largest(need):  # need is monotone in the count
+        lo, hi = 0, 1 << 26
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if need(mid) <= LAND_STEP:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    needs = {
+        "reduce": lambda c: r256(-(-c // n) * ext + 16) * n + r256(c * ext),
+        "rsb": lambda c: r256(c * ext + 16) * (n + 1),
+        "rs": lambda c: r256(c * ext + 16) * (n + 1),  # c: the largest block
+        "scan": lambda c: c * ext + 256,
+        "ag": lambda c: r256(c + 16) * n,  # c: bytes per rank
+    }
+    msgs = []
+    for j, kind in enumerate(("reduce", "rsb", "rs", "scan", "ag")):
+        c = largest(needs[kind])
+        root = n - 1
+        rcounts = [0 if r == 1 else c - 3 * r for r in range(n)]
+        total = {"rsb": c * n, "rs": sum(rcounts), "ag": -(-c // ext)}.get(kind, c)
+        xs = [inputs(F, total, r, salt + j) for r in range(n)]
+        if kind == "reduce":
+            exp, _ = orc.reduce([x.copy() for x in xs], c, SUM.index, F.code, root, True)
+            exp = exp if rank == root else None
+        elif kind == "rsb":
+            exp = orc.reduce_scatter_block([x.copy() for x in xs], c, SUM.index, F.code)[rank]
+        elif kind == "rs":
+            exp = orc.reduce_scatter([x.copy() for x in xs], rcounts, SUM.index, F.code)[0][rank]
+        elif kind == "scan":
+            exp = orc.scan([x.copy() for x in xs], c, SUM.index, F.code, False)[rank]
+        else:
+            exp = np.concatenate([x.view(np.uint8)[:c] for x in xs])
+        comms = []
+        try:
+            for blocking in (False, True):
+                if kind == "ag" and blocking:
+                    continue
+                cc = coll.Communicator.from_torch_distributed(device=comm.device)
+                comms.append(cc)
+                cc.set_param("timeout_ms", 20000)
+                cc.set_param("own_stream", 1)
+                landed0 = cc.get_param("landing_ag_bcast")
+                s = to_dev(xs[rank], extra=16)
+                if kind == "reduce":
+                    o = s if rank == root else None
+                    src = coll.IN_PLACE if rank == root else s
+                    go = ((lambda: cc.reduce(src, o, c, F, SUM, root, blocking=True)) if blocking else
+                          (lambda: cc.ireduce(src, o, c, F, SUM, root)))
+                elif kind == "rsb":
+                    o = torch.zeros(c * ext, dtype=torch.uint8, device="cuda")
+                    go = ((lambda: cc.reduce_scatter_block(s, o, c, F, SUM, blocking=True)) if blocking else
+                          (lambda: cc.ireduce_scatter_block(s, o, c, F, SUM)))
+                elif kind == "rs":
+                    o = torch.zeros((rcounts[rank] + 1) * ext, dtype=torch.uint8, device="cuda")
+                    go = ((lambda: cc.reduce_scatter(s, o, rcounts, F, SUM, blocking=True)) if blocking else
+                          (lambda: cc.ireduce_scatter(s, o, rcounts, F, SUM)))
+                elif kind == "scan":
+                    o = torch.zeros_like(s)
+                    go = ((lambda: cc.scan(s, o, c, F, SUM, blocking=True)) if blocking else
+                          (lambda: cc.iscan(s, o, c, F, SUM)))
+                else:
+                    o = torch.zeros(n * c, dtype=torch.uint8, device="cuda")
+                    go = lambda: cc.iallgather(s, o, c)  # noqa: E731
+                torch.cuda.synchronize()  # MPI semantics: the buffers are ready at the call
+                req = go()
+                if not blocking:
+                    req.wait()
+                    req.free()
+                torch.cuda.synchronize()
+                what = f"{kind} {c} {'blocking' if blocking else 'nonblocking'}"
+                if exp is not None:
+                    want = np.asarray(exp).view(np.uint8 if kind == "ag" else F.np_dtype)
+                    got = o.cpu().numpy().view(np.uint8)[:want.nbytes].view(want.dtype)
+                    ok, msg = checked(got, want)
+                    if not ok:
+                        msgs.append(f"{what}: {msg}")
+                if n > 1:
+                    lb, dg = cc.get_param("landing_bytes"), cc.get_param("landing_deferred_growths")
+                    if lb != LAND_STEP:
+                        msgs.append(f"{what}: landing_bytes {lb}, expected {LAND_STEP}")
+                    if not blocking and dg != 1:
+                        msgs.append(f"{what}: {dg} deferred growths, expected 1")
+                    if kind == "ag" and cc.get_param("landing_ag_bcast") <= landed0:
+                        msgs.append(f"{what}: did not take the landing path")
+                if cc.error():
+                    msgs.append(f"{what}: device error {cc.error()}")
+        finally:
+            for cc in comms:
+                cc.free()
+    return not msgs, "; ".join(msgs[:4])
+
+
 def case_cross_comm_random(comm, rank, n, salt, ncomm=3, per_comm=6):
     """Randomized MPI-path ordering (coll/rocm's own_stream): three
     communicators over the same ranks, each with a sequence of nonblocking
@@ -1824,6 +1938,9 @@ def main():
                   ("cross_comm_random_own_stream", lambda: case_cross_comm_random(comm, rank, n, 193 + STRESS_SEED)),
                   ("cross_comm_random_own_stream_b",
                    lambda: case_cross_comm_random(comm, rank, n, 194 + STRESS_SEED))]
+    if only and "nb_landing_sized_at_post" in only.split(","):
+        # by name only (test_coll_gpu.test_nb_landing_sized_at_post): ten fresh communicators
+        cases += [("nb_landing_sized_at_post", lambda: case_nb_landing_sized_at_post(comm, rank, n, 196))]
     if only and "cross_comm" in only:
         # opt-in: the known limitation of DESIGN.md §8 item 9 (device-side
         # waits across communicators posted in opposite orders time out)

@@ -151,3 +151,20 @@ def test_waits_without_host_marks_n3():
         if rc != 0 or bad or len(lines) != 7:
             failures.append((r, rc, bad[:3], [ln["case"] for ln in lines], out[-1500:]))
     assert not failures, failures
+
+
+@pytest.mark.parametrize("n", [2, 3])
+def test_nb_landing_sized_at_post(n):
+    """Nonblocking reduce / reduce_scatter(_block) / scan / allgather whose
+    landing need is the largest that fits the buffer's first 32 MiB step:
+    the post sizes the buffer for the launch (one deferred growth, exactly
+    one step), as the blocking call on another communicator does."""
+    outs = run_ranks(n, extra_env={"COLL_CASES": "nb_landing_sized_at_post"}, tag="landing_n")
+    failures = []
+    for r, (rc, out) in enumerate(outs):
+        lines = [json.loads(ln) for ln in out.splitlines() if ln.startswith("{")]
+        lines = [ln for ln in lines if ln["case"] != "ipc_mode"]
+        bad = [ln for ln in lines if not ln["ok"]]
+        if rc != 0 or bad or len(lines) != 1:
+            failures.append((r, rc, bad[:3], out[-1500:]))
+    assert not failures, failures
