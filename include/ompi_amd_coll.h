@@ -351,6 +351,76 @@ int ompi_amd_alltoallv_init(ompi_amd_comm_t *comm, const void *sbuf, const size_
                             const size_t *sdispls, void *rbuf, const size_t *rcounts,
                             const size_t *rdispls, ompi_amd_plan_t **plan);
 
+/* MPI_Allgatherv, MPI_Gather, MPI_Gatherv, MPI_Scatter, MPI_Scatterv
+ * (coll_allgatherv / coll_gather / coll_gatherv / coll_scatter /
+ * coll_scatterv and their nonblocking and persistent forms in coll.h).
+ * Counts and displacements are BYTES and are copied at post / init.  Each is
+ * the alltoall's exchange with a sparse or repeated count matrix and takes
+ * its three paths by the same thresholds (fused_bytes, small_bytes,
+ * alltoall_chunk); get_param "gather_fused" / "gather_staged" /
+ * "gather_landing" count these five collectives' calls per path and
+ * "gather_passes" their landing passes.  A small allgatherv runs as one
+ * launch that loads each vector of this rank's block once and stores it to
+ * every peer.
+ *   MPI_IN_PLACE is (void *)1: in sbuf at the root for gather(v), in rbuf at
+ * the root for scatter(v), in sbuf on every rank for allgatherv, which also
+ * takes sbuf == rbuf + rdispls[rank] as in place (as allgather does).  The
+ * rank's own block then stays where it is.
+ *   Arguments MPI calls "significant only at root" are ignored on the other
+ * ranks and may be NULL there: rbuf, rcounts, rdispls of gather(v); sbuf,
+ * scounts, sdispls of scatter(v).
+ *   OMPI_AMD_ERR_BAD_PARAM, before any device work and with no request or
+ * plan coming back: a NULL communicator; a root outside [0, size); a NULL
+ * significant buffer with bytes > 0; a NULL significant count or
+ * displacement array; a NULL request / plan pointer; sbytes !=
+ * rcounts[rank] in allgatherv when not in place; sbytes != rcounts[root] at
+ * the gatherv root when not in place, rbytes != scounts[root] at the
+ * scatterv root likewise.
+ *   size == 1 is one local copy, or nothing in place.  A call whose largest
+ * pair is 0 bytes does nothing on any rank.
+ *   allgatherv (rcounts are the same on every rank), gather and scatter (one
+ * count) know the call's largest pair locally: no host rendezvous in the
+ * blocking call below the landing path, in the i* forms or in any plan
+ * start, and their *_init is local.  gatherv and scatterv agree on it as
+ * alltoallv does: one host allgather in the blocking call, a posted ticket
+ * in igatherv / iscatterv, once at gatherv_init / scatterv_init (which are
+ * therefore collective).  Plans are of kind 4. */
+int ompi_amd_allgatherv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                        const size_t *rcounts, const size_t *rdispls, void *stream);
+int ompi_amd_gather(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                    void *stream);
+int ompi_amd_scatter(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                     void *stream);
+int ompi_amd_gatherv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                     const size_t *rcounts, const size_t *rdispls, int root, void *stream);
+int ompi_amd_scatterv(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                      const size_t *sdispls, void *rbuf, size_t rbytes, int root, void *stream);
+int ompi_amd_iallgatherv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                         const size_t *rcounts, const size_t *rdispls, void *stream,
+                         ompi_amd_request_t **request);
+int ompi_amd_igather(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                     void *stream, ompi_amd_request_t **request);
+int ompi_amd_iscatter(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                      void *stream, ompi_amd_request_t **request);
+int ompi_amd_igatherv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                      const size_t *rcounts, const size_t *rdispls, int root, void *stream,
+                      ompi_amd_request_t **request);
+int ompi_amd_iscatterv(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                       const size_t *sdispls, void *rbuf, size_t rbytes, int root, void *stream,
+                       ompi_amd_request_t **request);
+int ompi_amd_allgatherv_init(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                             const size_t *rcounts, const size_t *rdispls, ompi_amd_plan_t **plan);
+int ompi_amd_gather_init(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                         ompi_amd_plan_t **plan);
+int ompi_amd_scatter_init(ompi_amd_comm_t *comm, const void *sbuf, void *rbuf, size_t bytes, int root,
+                          ompi_amd_plan_t **plan);
+int ompi_amd_gatherv_init(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, void *rbuf,
+                          const size_t *rcounts, const size_t *rdispls, int root,
+                          ompi_amd_plan_t **plan);
+int ompi_amd_scatterv_init(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                           const size_t *sdispls, void *rbuf, size_t rbytes, int root,
+                           ompi_amd_plan_t **plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,23 @@ PROTOTYPES = [
     ("ompi_amd_alltoallv_init", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
       _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_void_p)]),
+] + [
+    # allgatherv / gather(v) / scatter(v): blocking (.., stream), nonblocking
+    # (.., stream, request *) and persistent (.., plan *) forms of one operand list
+    (f"ompi_amd_{pre}{name}{post}", _C.c_int, [_C.c_void_p] + ops + tail)
+    for name, ops in [
+        ("allgatherv", [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_size_t),
+                        _C.POINTER(_C.c_size_t)]),
+        ("gather", [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int]),
+        ("scatter", [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int]),
+        ("gatherv", [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_size_t),
+                     _C.POINTER(_C.c_size_t), _C.c_int]),
+        ("scatterv", [_C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+                      _C.c_size_t, _C.c_int]),
+    ]
+    for pre, post, tail in [("", "", [_C.c_void_p]), ("i", "", [_C.c_void_p, _C.POINTER(_C.c_void_p)]),
+                            ("", "_init", [_C.POINTER(_C.c_void_p)])]
+] + [
     # point-to-point (include/ompi_amd_p2p.h)
     ("ompi_amd_isend", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,

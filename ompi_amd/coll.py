@@ -14,6 +14,10 @@ Mirrors the coll framework's entry points this path provides
     coll_bcast(buf, count, dtype, root, comm, module)
     coll_alltoall(sbuf, scount, sdtype, rbuf, rcount, rdtype, comm, module)
     coll_alltoallv(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm, module)
+    coll_allgatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, comm, module)
+    coll_gather / coll_scatter(sbuf, scount, sdtype, rbuf, rcount, rdtype, root, comm, module)
+    coll_gatherv(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, root, comm, module)
+    coll_scatterv(sbuf, scounts, disps, sdtype, rbuf, rcount, rdtype, root, comm, module)
 
 with the communicator object holding the module state (IPC mappings, flags,
 epoch).  One process per GPU on one node.  All calls are stream-ordered;
@@ -44,6 +48,11 @@ def _ptr(buf) -> int:
             raise _lib.OmpiAmdError(_lib.ERR_NOT_DEVICE, "host tensor passed to a device collective")
         return buf.data_ptr()
     raise TypeError(type(buf))
+
+
+def _optr(buf):
+    """_ptr, with None for an operand that is not significant on this rank."""
+    return None if buf is None else _ptr(buf)
 
 
 def _stream(stream):
@@ -240,6 +249,96 @@ class Communicator:
         rc = self._lib.ompi_amd_alltoallv(self._h, *self._v_args(sbuf, scounts, sdispls, rbuf, rcounts,
                                                                  rdispls), _stream(stream))
         self._finish(rc, "alltoallv", blocking, stream)
+
+    # -- allgatherv / gather(v) / scatter(v) ----------------------------------
+    # Counts and displacements are lists of bytes.  Operands MPI calls
+    # "significant only at root" may be None on the other ranks.  IN_PLACE:
+    # sbuf at the root of gather(v), rbuf at the root of scatter(v), sbuf on
+    # every rank of allgatherv.
+    def _osizes(self, values):
+        return ctypes.POINTER(ctypes.c_size_t)() if values is None else self._sizes(values)
+
+    def _xch(self, name: str, form: int, args, stream=None, blocking: bool = False):
+        """One of the five in its blocking (0), nonblocking (1) or
+        persistent (2) form."""
+        what = (name, "i" + name, name + "_init")[form]
+        fn = getattr(self._lib, "ompi_amd_" + what)
+        if form == 0:
+            self._finish(fn(self._h, *args, _stream(stream)), what, blocking, stream)
+            return None
+        h = ctypes.c_void_p()
+        if form == 1:
+            _lib.check(fn(self._h, *args, _stream(stream), ctypes.byref(h)), what)
+            return Request(self, h, what)
+        _lib.check(fn(self._h, *args, ctypes.byref(h)), what)
+        return Plan(self, h, name)
+
+    def _agv_args(self, sbuf, sbytes, rbuf, rcounts, rdispls):
+        return (_optr(sbuf), int(sbytes), _optr(rbuf), self._osizes(rcounts), self._osizes(rdispls))
+
+    def allgatherv(self, sbuf, sbytes: int, rbuf, rcounts, rdispls, stream=None,
+                   blocking: bool = False) -> None:
+        """MPI_Allgatherv: my `sbytes` go to rdispls[rank] of every rank's
+        rbuf (sbuf IN_PLACE: they are there already)."""
+        self._xch("allgatherv", 0, self._agv_args(sbuf, sbytes, rbuf, rcounts, rdispls), stream, blocking)
+
+    def iallgatherv(self, sbuf, sbytes: int, rbuf, rcounts, rdispls, stream=None) -> "Request":
+        return self._xch("allgatherv", 1, self._agv_args(sbuf, sbytes, rbuf, rcounts, rdispls), stream)
+
+    def allgatherv_init(self, sbuf, sbytes: int, rbuf, rcounts, rdispls) -> "Plan":
+        """MPI_Allgatherv_init: local; the starts make no host rendezvous."""
+        return self._xch("allgatherv", 2, self._agv_args(sbuf, sbytes, rbuf, rcounts, rdispls))
+
+    def gather(self, sbuf, rbuf, nbytes: int, root: int, stream=None, blocking: bool = False) -> None:
+        """MPI_Gather: `nbytes` of every rank to block [rank] of the root's rbuf."""
+        self._xch("gather", 0, (_optr(sbuf), _optr(rbuf), int(nbytes), root), stream, blocking)
+
+    def igather(self, sbuf, rbuf, nbytes: int, root: int, stream=None) -> "Request":
+        return self._xch("gather", 1, (_optr(sbuf), _optr(rbuf), int(nbytes), root), stream)
+
+    def gather_init(self, sbuf, rbuf, nbytes: int, root: int) -> "Plan":
+        return self._xch("gather", 2, (_optr(sbuf), _optr(rbuf), int(nbytes), root))
+
+    def scatter(self, sbuf, rbuf, nbytes: int, root: int, stream=None, blocking: bool = False) -> None:
+        """MPI_Scatter: block [q] (`nbytes`) of the root's sbuf to rank q's rbuf."""
+        self._xch("scatter", 0, (_optr(sbuf), _optr(rbuf), int(nbytes), root), stream, blocking)
+
+    def iscatter(self, sbuf, rbuf, nbytes: int, root: int, stream=None) -> "Request":
+        return self._xch("scatter", 1, (_optr(sbuf), _optr(rbuf), int(nbytes), root), stream)
+
+    def scatter_init(self, sbuf, rbuf, nbytes: int, root: int) -> "Plan":
+        return self._xch("scatter", 2, (_optr(sbuf), _optr(rbuf), int(nbytes), root))
+
+    def _gv_args(self, sbuf, sbytes, rbuf, rcounts, rdispls, root):
+        return self._agv_args(sbuf, sbytes, rbuf, rcounts, rdispls) + (root,)
+
+    def gatherv(self, sbuf, sbytes: int, rbuf, rcounts, rdispls, root: int, stream=None,
+                blocking: bool = False) -> None:
+        """MPI_Gatherv: rank p's `sbytes` to rdispls[p] of the root's rbuf."""
+        self._xch("gatherv", 0, self._gv_args(sbuf, sbytes, rbuf, rcounts, rdispls, root), stream, blocking)
+
+    def igatherv(self, sbuf, sbytes: int, rbuf, rcounts, rdispls, root: int, stream=None) -> "Request":
+        return self._xch("gatherv", 1, self._gv_args(sbuf, sbytes, rbuf, rcounts, rdispls, root), stream)
+
+    def gatherv_init(self, sbuf, sbytes: int, rbuf, rcounts, rdispls, root: int) -> "Plan":
+        """MPI_Gatherv_init: collective (the ranks agree on the largest
+        count once); the starts make no host rendezvous."""
+        return self._xch("gatherv", 2, self._gv_args(sbuf, sbytes, rbuf, rcounts, rdispls, root))
+
+    def _sv_args(self, sbuf, scounts, sdispls, rbuf, rbytes, root):
+        return (_optr(sbuf), self._osizes(scounts), self._osizes(sdispls), _optr(rbuf), int(rbytes), root)
+
+    def scatterv(self, sbuf, scounts, sdispls, rbuf, rbytes: int, root: int, stream=None,
+                 blocking: bool = False) -> None:
+        """MPI_Scatterv: scounts[q] bytes at sdispls[q] of the root's sbuf to rank q."""
+        self._xch("scatterv", 0, self._sv_args(sbuf, scounts, sdispls, rbuf, rbytes, root), stream, blocking)
+
+    def iscatterv(self, sbuf, scounts, sdispls, rbuf, rbytes: int, root: int, stream=None) -> "Request":
+        return self._xch("scatterv", 1, self._sv_args(sbuf, scounts, sdispls, rbuf, rbytes, root), stream)
+
+    def scatterv_init(self, sbuf, scounts, sdispls, rbuf, rbytes: int, root: int) -> "Plan":
+        """MPI_Scatterv_init: collective, as gatherv_init."""
+        return self._xch("scatterv", 2, self._sv_args(sbuf, scounts, sdispls, rbuf, rbytes, root))
 
     # -- nonblocking forms (coll.h:261-410) -----------------------------------
     def ialltoall(self, sbuf, rbuf, nbytes: int, stream=None) -> "Request":

@@ -375,12 +375,19 @@ struct shadow_set {
 
 // One alltoall / alltoallv as every path sees it: bytes, MPI_IN_PLACE
 // resolved (the send side is then the receive side, as MPI defines).
+// allgatherv, gather(v) and scatter(v) are the same exchange with sparse or
+// repeated rows; `coll` keeps their counters, their fused
+// kernel and their landing layout apart.
+enum { XCH_ALLTOALL = 0, XCH_ALLGATHERV = 1, XCH_GATHER = 2, XCH_SCATTER = 3 };
 struct a2a_call {
     const char *sbuf;
     char *rbuf;
-    bool inplace;
-    bool uniform;  // alltoall: both ends know both offsets of a block (the phase rule)
-    size_t B;      // uniform: bytes per pair
+    bool inplace;  // my own block stays where it is
+    int coll;      // XCH_*
+    // Phase mod 16 of sender p's block inside its slot: the receiver's rbuf
+    // offset where both ends of the pair know it (alltoall, gather: p * B;
+    // allgatherv: rdispls[p]), else 0.
+    uint8_t ph[kMaxRanks];
     size_t sc[kMaxRanks], sd[kMaxRanks], rc[kMaxRanks], rd[kMaxRanks];
 };
 
@@ -626,6 +633,10 @@ struct ompi_amd_comm {
     size_t alltoall_chunk = 0;
     int64_t alltoall_passes = 0;
     int64_t alltoall_paths[5] = {};  // calls per path (A2A_*), get_param "alltoall_fused" / _staged / _landing
+    // the same for allgatherv / gather(v) / scatter(v): "gather_fused" /
+    // _staged / _landing / _passes
+    int64_t gather_paths[5] = {};
+    int64_t gather_passes = 0;
     // param "copy_nt": 1 the copy and fold kernels store non-temporally —
     // measured no slower on one GPU at N = 2 / 4 / 8 (scatter, gather and fold
     // kernels 1-5 % faster) — 0 plain stores; -1 (default)
@@ -3610,6 +3621,10 @@ int ompi_amd_comm_get_param(const ompi_amd_comm_t *c, const char *key, int64_t *
     else if (!strcmp(key, "alltoall_fused")) *v = c->alltoall_paths[2];
     else if (!strcmp(key, "alltoall_staged")) *v = c->alltoall_paths[3];
     else if (!strcmp(key, "alltoall_landing")) *v = c->alltoall_paths[4];
+    else if (!strcmp(key, "gather_passes")) *v = c->gather_passes;
+    else if (!strcmp(key, "gather_fused")) *v = c->gather_paths[2];
+    else if (!strcmp(key, "gather_staged")) *v = c->gather_paths[3];
+    else if (!strcmp(key, "gather_landing")) *v = c->gather_paths[4];
     else if (!strcmp(key, "copy_nt")) *v = c->copy_nt;
     else if (!strcmp(key, "copy_nt_fixed")) *v = c->copy_nt_fixed;
     else if (!strcmp(key, "unsafe_exports")) *v = c->unsafe_exports;
@@ -4580,8 +4595,19 @@ static int a2a_path(const ompi_amd_comm_t *c, const path_params &pp, size_t M) {
     return A2A_LAND;
 }
 
-static size_t a2a_phase(const a2a_call &k, int sender) {
-    return k.uniform ? ((size_t)sender * k.B) & 15 : 0;
+static size_t a2a_phase(const a2a_call &k, int sender) { return k.ph[sender]; }
+
+// slots of one rank's landing buffer per pass, and the slot sender p stores into
+static int a2a_slots(const ompi_amd_comm_t *c, const a2a_call &k) {
+    return k.coll == XCH_SCATTER ? scatter_slots(c->size) : c->size;
+}
+static land_layout a2a_landing(const ompi_amd_comm_t *c, const a2a_call &k, size_t chunk, size_t M) {
+    switch (k.coll) {
+    case XCH_ALLGATHERV: return allgatherv_landing(c->size, chunk, M);
+    case XCH_GATHER: return gather_landing(c->size, chunk, M);
+    case XCH_SCATTER: return scatter_landing(c->size, chunk, M);
+    default: return alltoall_landing(c->size, chunk, M);
+    }
 }
 
 static void a2a_uniform(const ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t B, a2a_call *k) {
@@ -4589,11 +4615,10 @@ static void a2a_uniform(const ompi_amd_comm_t *c, const void *sbuf, void *rbuf, 
     k->inplace = in_place(sbuf, rbuf);
     k->sbuf = (const char *)(k->inplace ? rbuf : sbuf);
     k->rbuf = (char *)rbuf;
-    k->uniform = true;
-    k->B = B;
     for (int p = 0; p < c->size; ++p) {
         k->sc[p] = k->rc[p] = B;
         k->sd[p] = k->rd[p] = (size_t)p * B;
+        k->ph[p] = (uint8_t)(((size_t)p * B) & 15);
     }
 }
 
@@ -4609,6 +4634,71 @@ static void a2a_vector(const ompi_amd_comm_t *c, const void *sbuf, const size_t 
         k->sc[p] = k->inplace ? rc[p] : sc[p];
         k->sd[p] = k->inplace ? rd[p] : sd[p];
     }
+}
+
+// allgatherv: every send displacement equal (my one block goes to every
+// peer); rcounts / rdispls are the same on every rank, so the phase can
+// follow the receiver's offset.  In place: (void *)1 or sbuf already at its
+// place in rbuf.
+static void a2a_allgatherv(const ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf,
+                           const size_t *rc, const size_t *rd, a2a_call *k) {
+    *k = a2a_call{};
+    k->coll = XCH_ALLGATHERV;
+    char *mine = (char *)rbuf + rd[c->rank];
+    k->inplace = sbuf == (const void *)1 || sbuf == (const void *)mine;
+    k->sbuf = k->inplace ? mine : (const char *)sbuf;
+    k->rbuf = (char *)rbuf;
+    for (int p = 0; p < c->size; ++p) {
+        k->sc[p] = k->inplace ? rc[c->rank] : sbytes;
+        k->rc[p] = rc[p];
+        k->rd[p] = rd[p];
+        k->ph[p] = (uint8_t)(rd[p] & 15);
+    }
+}
+
+// gather(v): only the root's receive row is non-zero.  B != 0: the uniform
+// gather of B bytes (rc / rd null; block p at p * B, which every rank knows
+// and the phase follows); gatherv passes B = 0 and the root its rc / rd.
+static void a2a_gather(const ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, size_t B,
+                       const size_t *rc, const size_t *rd, int root, a2a_call *k) {
+    *k = a2a_call{};
+    k->coll = XCH_GATHER;
+    const bool at_root = c->rank == root;
+    if (at_root) {
+        k->rbuf = (char *)rbuf;
+        for (int p = 0; p < c->size; ++p) {
+            k->rc[p] = rc ? rc[p] : B;
+            k->rd[p] = rd ? rd[p] : (size_t)p * B;
+        }
+        const char *mine = k->rbuf + k->rd[root];
+        k->inplace = sbuf == (const void *)1 || sbuf == (const void *)mine;
+        sbytes = k->inplace ? k->rc[root] : sbytes;
+    }
+    k->sbuf = k->inplace ? k->rbuf + k->rd[root] : (const char *)sbuf;
+    k->sc[root] = sbytes;
+    if (B)
+        for (int p = 0; p < c->size; ++p) k->ph[p] = (uint8_t)(((size_t)p * B) & 15);
+}
+
+// scatter(v): only the root's send row is non-zero; a receiver's block lands
+// at offset 0 of its rbuf, but the root cannot know that buffer's phase.
+static void a2a_scatter(const ompi_amd_comm_t *c, const void *sbuf, size_t B, const size_t *sc,
+                        const size_t *sd, void *rbuf, size_t rbytes, int root, a2a_call *k) {
+    *k = a2a_call{};
+    k->coll = XCH_SCATTER;
+    const bool at_root = c->rank == root;
+    k->rbuf = (char *)rbuf;
+    if (at_root) {
+        k->sbuf = (const char *)sbuf;
+        for (int p = 0; p < c->size; ++p) {
+            k->sc[p] = sc ? sc[p] : B;
+            k->sd[p] = sd ? sd[p] : (size_t)p * B;
+        }
+        k->inplace = rbuf == (void *)1 || (const char *)rbuf == k->sbuf + k->sd[root];
+        if (k->inplace) k->rbuf = const_cast<char *>(k->sbuf) + k->sd[root];
+        rbytes = k->sc[root];
+    }
+    k->rc[root] = rbytes;
 }
 
 // the largest pair this rank sees: its row and its column of the count matrix
@@ -4652,7 +4742,12 @@ static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipSt
         a.mark = c->mark_word;
         a.mark_v = mark_reserve();
     }
-    if (c->copy_nt)
+    if (k.coll == XCH_ALLGATHERV) {  // one block to every peer: load once, store N times
+        if (c->copy_nt)
+            hipLaunchKernelGGL(fused_allgatherv_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL(fused_allgatherv_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, a);
+    } else if (c->copy_nt)
         hipLaunchKernelGGL(fused_alltoall_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, a);
     else
         hipLaunchKernelGGL(fused_alltoall_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, a);
@@ -4663,11 +4758,13 @@ static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipSt
 
 // One exchange of bytes [off, off + chunk) of every pair through slots of
 // `slot` bytes: `mine` is where my peers' stores land, peers.p[q] the same
-// memory of rank q as mapped here.
+// memory of rank q as mapped here.  Sender p's block sits in slot [p], or in
+// slot [0] where the layout has one slot (the scatter's landing buffer).
 static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, size_t chunk,
-                             char *mine, const ptr_set &peers, size_t slot, bool trailing,
+                             char *mine, const ptr_set &peers, size_t slot, int slots, bool trailing,
                              hipStream_t s) {
     const int n = c->size, me = c->rank;
+    auto at = [&](int p) { return (size_t)(slots == 1 ? 0 : p) * slot + a2a_phase(k, p); };
     auto piece = [&](size_t cnt, size_t *lo, size_t *len) {
         *lo = std::min(cnt, off);
         *len = std::min(cnt, off + chunk) - *lo;
@@ -4679,7 +4776,7 @@ static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, 
         piece(k.sc[q], &lo, &len);
         if (!len || (i == 0 && k.inplace)) continue;
         char *d = i == 0 ? k.rbuf + k.rd[me] + lo
-                         : const_cast<char *>(peers.p[q]) + (size_t)me * slot + a2a_phase(k, me);
+                         : const_cast<char *>(peers.p[q]) + at(me);
         cj.j[cj.n++] = {k.sbuf + k.sd[q] + lo, d, (int64_t)len};
     }
     TRY(launch_copy(c, cj, s));
@@ -4688,7 +4785,7 @@ static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, 
     for (int p = 0; p < n; ++p) {
         piece(k.rc[p], &lo, &len);
         if (!len || p == me) continue;
-        cj.j[cj.n++] = {mine + (size_t)p * slot + a2a_phase(k, p), k.rbuf + k.rd[p] + lo, (int64_t)len};
+        cj.j[cj.n++] = {mine + at(p), k.rbuf + k.rd[p] + lo, (int64_t)len};
     }
     TRY(launch_copy(c, cj, s));
     return trailing ? launch_barrier(c, s) : OMPI_AMD_SUCCESS;
@@ -4697,14 +4794,15 @@ static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, 
 static int alltoall_land(ompi_amd_comm_t *c, const a2a_call &k, size_t M, size_t chunk, bool may_grow,
                          hipStream_t s) {
     chunk = std::min(chunk, M);
-    const size_t need = alltoall_landing(c->size, chunk, M).need;
+    const int slots = a2a_slots(c, k);
+    const size_t need = a2a_landing(c, k, chunk, M).need;
     if (need > c->land_bytes) {
         if (may_grow) {  // collective: every rank computes the same need
             TRY(ensure_landing(c, need));
         } else {
             // a deferred call runs in passes the landing buffer it finds can
             // hold (the same on every rank: growths switch at one queue position)
-            const size_t fit = alltoall_fit_chunk(c->size, c->land_bytes);
+            const size_t fit = alltoall_fit_chunk(slots, c->land_bytes);
             if (!fit) {
                 record_msg("alltoall: no landing buffer for a deferred call (%zu B)", c->land_bytes);
                 return OMPI_AMD_ERR_UNSUPPORTED;
@@ -4712,10 +4810,10 @@ static int alltoall_land(ompi_amd_comm_t *c, const a2a_call &k, size_t M, size_t
             chunk = std::min(chunk, fit);
         }
     }
-    const size_t slot = alltoall_landing(c->size, chunk, M).slot;
+    const size_t slot = a2a_landing(c, k, chunk, M).slot;
     for (size_t off = 0; off < M; off += chunk) {
-        TRY(alltoall_exchange(c, k, off, chunk, c->land, c->peer_land, slot, true, s));
-        ++c->alltoall_passes;
+        TRY(alltoall_exchange(c, k, off, chunk, c->land, c->peer_land, slot, slots, true, s));
+        ++(k.coll == XCH_ALLTOALL ? c->alltoall_passes : c->gather_passes);
     }
     return OMPI_AMD_SUCCESS;
 }
@@ -4723,7 +4821,7 @@ static int alltoall_land(ompi_amd_comm_t *c, const a2a_call &k, size_t M, size_t
 static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const path_params &pp,
                         size_t chunk, bool may_grow, hipStream_t s) {
     const int path = a2a_path(c, pp, M);
-    ++c->alltoall_paths[path];
+    ++(k.coll == XCH_ALLTOALL ? c->alltoall_paths : c->gather_paths)[path];
     if (path == A2A_NONE) return OMPI_AMD_SUCCESS;
     TRY(set_dev(c));
     if (path == A2A_LOCAL) {
@@ -4735,7 +4833,7 @@ static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const p
     if (path == A2A_STAGED) {
         // no trailing barrier: the halves alternate (next_half)
         const stage_half sh = next_half(c);
-        return alltoall_exchange(c, k, 0, M, sh.mine, sh.peers, ag_land_slot(M), false, s);
+        return alltoall_exchange(c, k, 0, M, sh.mine, sh.peers, ag_land_slot(M), c->size, false, s);
     }
     return alltoall_land(c, k, M, chunk, may_grow, s);
 }
@@ -4824,8 +4922,8 @@ static int ia2a_post(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree
     if (n == 1) agree = false;
     o.a2a_M = agree ? 0 : M;
     size_t need = 0;
-    if (agree) need = alltoall_landing(c->size, o.a2a_chunk, kA2avNbChunk).need;
-    else if (a2a_path(c, o.pp, M) == A2A_LAND) need = alltoall_landing(c->size, o.a2a_chunk, M).need;
+    if (agree) need = a2a_landing(c, k, o.a2a_chunk, kA2avNbChunk).need;
+    else if (a2a_path(c, o.pp, M) == A2A_LAND) need = a2a_landing(c, k, o.a2a_chunk, M).need;
     if (need) TRY(nb_grow_landing(c, need, req, o.stream));
     if (!agree) return nb_post(c, o, nullptr, 0, false, out);
     call_blob mine{};
@@ -4857,6 +4955,135 @@ int ompi_amd_ialltoallv(ompi_amd_comm_t *c, const void *sbuf, const size_t *scou
     a2a_vector(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, &k);
     return ia2a_post(c, k, a2a_local_max(c, k), true, stream, out);
 }
+
+// ---- allgatherv / gather(v) / scatter(v) ----
+// Each is the exchange above with a sparse or repeated count matrix, entered
+// in one of three forms.  allgatherv, gather and scatter know their largest
+// pair locally (rcounts are the same on every rank; one count), so they never
+// meet on the host below the blocking landing growth; gatherv and scatterv
+// agree as alltoallv does (a non-root sees only its own count).
+static int plan_nb_new(ompi_amd_comm_t *c, int nb_kind, const void *src, void *rbuf, size_t count,
+                       int type, int op, int root, size_t bytes, ompi_amd_plan_t **out);
+
+enum { XF_BLOCKING = 0, XF_POST = 1, XF_INIT = 2 };
+struct xch_form {
+    int form;
+    void *stream;
+    void **out;  // XF_POST: the request; XF_INIT: the plan
+};
+
+// the checks every form shares; nothing comes back from a refused call
+static int xch_form_ok(const ompi_amd_comm_t *c, const xch_form &f) {
+    if (f.form != XF_BLOCKING) {
+        if (!f.out) return OMPI_AMD_ERR_BAD_PARAM;
+        *f.out = nullptr;
+    }
+    return c ? OMPI_AMD_SUCCESS : OMPI_AMD_ERR_BAD_PARAM;
+}
+
+static int xch_enter(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree, const xch_form &f) {
+    if (f.form == XF_POST) return ia2a_post(c, k, M, agree, f.stream, (ompi_amd_request_t **)f.out);
+    if (f.form == XF_BLOCKING || agree) {
+        TRY(check_sticky(c));
+        TRY(drain(c));
+        if (agree) TRY(a2av_agree(c, k, &M));
+    }
+    if (f.form == XF_BLOCKING)
+        return alltoall_run(c, k, M, params_of(c), a2a_chunk_of(c), true, comm_stream(c, f.stream));
+    ompi_amd_plan_t **pl = (ompi_amd_plan_t **)f.out;
+    TRY(plan_nb_new(c, PEND_ALLTOALL, k.sbuf, k.rbuf, 0, 0, 0, 0, 0, pl));
+    (*pl)->a2a = k;
+    (*pl)->a2a_M = M;
+    return OMPI_AMD_SUCCESS;
+}
+
+static int allgatherv_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf,
+                            const size_t *rc, const size_t *rd, const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    if (!rc || !rd) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_allgatherv(c, sbuf, sbytes, rbuf, rc, rd, &k);
+    size_t M = 0;
+    for (int p = 0; p < c->size; ++p) M = std::max(M, rc[p]);
+    if (M > 0 && !rbuf) return OMPI_AMD_ERR_BAD_PARAM;
+    if (!k.inplace && (sbytes != rc[c->rank] || (sbytes > 0 && !sbuf))) return OMPI_AMD_ERR_BAD_PARAM;
+    return xch_enter(c, k, M, false, f);
+}
+
+// B != 0 or rc == null at the root: the uniform gather (see a2a_gather)
+static int gather_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, size_t B,
+                        const size_t *rc, const size_t *rd, int root, bool vec, const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
+    const bool at_root = c->rank == root;
+    if (at_root && vec && (!rc || !rd)) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_gather(c, sbuf, sbytes, rbuf, B, vec ? rc : nullptr, vec ? rd : nullptr, root, &k);
+    if (at_root) {
+        size_t most = 0;
+        for (int p = 0; p < c->size; ++p) most = std::max(most, k.rc[p]);
+        if (most > 0 && !rbuf) return OMPI_AMD_ERR_BAD_PARAM;
+        if (!k.inplace && sbytes != k.rc[root]) return OMPI_AMD_ERR_BAD_PARAM;
+    }
+    if (!k.inplace && sbytes > 0 && (!sbuf || sbuf == (const void *)1)) return OMPI_AMD_ERR_BAD_PARAM;
+    return xch_enter(c, k, vec ? a2a_local_max(c, k) : B, vec, f);
+}
+
+static int scatter_enter(ompi_amd_comm_t *c, const void *sbuf, size_t B, const size_t *sc,
+                         const size_t *sd, void *rbuf, size_t rbytes, int root, bool vec,
+                         const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
+    const bool at_root = c->rank == root;
+    if (at_root && vec && (!sc || !sd)) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_scatter(c, sbuf, B, vec ? sc : nullptr, vec ? sd : nullptr, rbuf, rbytes, root, &k);
+    if (at_root) {
+        size_t most = 0;
+        for (int p = 0; p < c->size; ++p) most = std::max(most, k.sc[p]);
+        if (most > 0 && !sbuf) return OMPI_AMD_ERR_BAD_PARAM;
+        if (!k.inplace && rbytes != k.sc[root]) return OMPI_AMD_ERR_BAD_PARAM;
+    }
+    if (!k.inplace && rbytes > 0 && (!rbuf || rbuf == (void *)1)) return OMPI_AMD_ERR_BAD_PARAM;
+    return xch_enter(c, k, vec ? a2a_local_max(c, k) : B, vec, f);
+}
+
+#define XCH_FORMS(name, PARAMS, CALL)                                                          \
+    int ompi_amd_##name(PARAMS, void *stream) {                                                \
+        api_guard api_(c);                                                                     \
+        const xch_form f{XF_BLOCKING, stream, nullptr};                                        \
+        return CALL;                                                                           \
+    }                                                                                          \
+    int ompi_amd_i##name(PARAMS, void *stream, ompi_amd_request_t **out) {                     \
+        api_guard api_(c);                                                                     \
+        const xch_form f{XF_POST, stream, (void **)out};                                       \
+        return CALL;                                                                           \
+    }                                                                                          \
+    int ompi_amd_##name##_init(PARAMS, ompi_amd_plan_t **out) {                                \
+        api_guard api_(c);                                                                     \
+        const xch_form f{XF_INIT, nullptr, (void **)out};                                      \
+        return CALL;                                                                           \
+    }
+#define XCH_P(...) __VA_ARGS__
+
+XCH_FORMS(allgatherv,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
+                const size_t *rdispls),
+          allgatherv_enter(c, sbuf, sbytes, rbuf, rcounts, rdispls, f))
+XCH_FORMS(gather, XCH_P(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, int root),
+          gather_enter(c, sbuf, bytes, rbuf, bytes, nullptr, nullptr, root, false, f))
+XCH_FORMS(scatter, XCH_P(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t bytes, int root),
+          scatter_enter(c, sbuf, bytes, nullptr, nullptr, rbuf, bytes, root, false, f))
+XCH_FORMS(gatherv,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, const size_t *rcounts,
+                const size_t *rdispls, int root),
+          gather_enter(c, sbuf, sbytes, rbuf, 0, rcounts, rdispls, root, true, f))
+XCH_FORMS(scatterv,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                void *rbuf, size_t rbytes, int root),
+          scatter_enter(c, sbuf, 0, scounts, sdispls, rbuf, rbytes, root, true, f))
+#undef XCH_FORMS
+#undef XCH_P
 
 int ompi_amd_allreduce_init(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count,
                             int type, int op, ompi_amd_plan_t **out) {

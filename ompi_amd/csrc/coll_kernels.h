@@ -775,6 +775,127 @@ __global__ __launch_bounds__(kXferThreads) void fused_alltoall_kernel(a2a_args a
     }
 }
 
+// ---------------------------------------------------------------- fused small allgatherv
+// The alltoall kernel above with every send displacement equal would read my
+// block once per destination.  This one runs on the same protocol, flag rows
+// and a2a_args (scount / sdispl[rank] describe my block; sphase[rank] is its
+// phase in the peers' slots), but workgroup g LOADS each 16-B vector of its
+// slice once and STORES it to my own rbuf position (unless in place) and to
+// slot [me] of every peer's scratch half, peers in the order me+1, me+2, ...
+// That needs the source and every destination at one phase mod 16; if they
+// are not, each destination gets its own pipe_copy, as in the alltoall.
+// The second half — drain, barrier, one release, signal, wait, acquire, copy
+// the slots out, mark — is the alltoall kernel's, statement for statement.
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void fused_allgatherv_kernel(a2a_args a) {
+    const int t = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+    int64_t lo, hi;
+    a2a_slice(a.scount[a.rank], g, G, &lo, &hi);
+    if (hi > lo) {
+        const char *s = a.sbuf + a.sdispl[a.rank];
+        char *own = a.rbuf + a.rdispl[a.rank];
+        const int64_t at = (int64_t)a.rank * a.slot + a.sphase[a.rank];  // my block in a peer's half
+        const uintptr_t ph = (uintptr_t)(s + lo) & 15;
+        bool same = !a.self_copy || ((uintptr_t)(own + lo) & 15) == ph;
+        for (int k = 1; k < a.n; ++k)
+            same = same && ((uintptr_t)(a.peers.p[(a.rank + k) % a.n] + at + lo) & 15) == ph;
+        if (same) {
+            const int64_t head = min(hi - lo, (int64_t)((16 - ph) & 15));
+            const int64_t nv = (hi - lo - head) / 16;
+            const int64_t body = lo + head;
+            const u32x4 *sv = reinterpret_cast<const u32x4 *>(s + body);
+            constexpr int S = kXferThreads;
+            int64_t i = t;
+            for (; i + 3 * S < nv; i += 4 * S) {  // 4 loads in flight per lane, as pipe_copy
+                const u32x4 v0 = __builtin_nontemporal_load(sv + i);
+                const u32x4 v1 = __builtin_nontemporal_load(sv + i + S);
+                const u32x4 v2 = __builtin_nontemporal_load(sv + i + 2 * S);
+                const u32x4 v3 = __builtin_nontemporal_load(sv + i + 3 * S);
+                if (a.self_copy) {
+                    u32x4 *dv = reinterpret_cast<u32x4 *>(own + body);
+                    dv[i] = v0;
+                    dv[i + S] = v1;
+                    dv[i + 2 * S] = v2;
+                    dv[i + 3 * S] = v3;
+                }
+                for (int k = 1; k < a.n; ++k) {
+                    u32x4 *dv = reinterpret_cast<u32x4 *>(
+                        const_cast<char *>(a.peers.p[(a.rank + k) % a.n]) + at + body);
+                    if (NT) {
+                        __builtin_nontemporal_store(v0, dv + i);
+                        __builtin_nontemporal_store(v1, dv + i + S);
+                        __builtin_nontemporal_store(v2, dv + i + 2 * S);
+                        __builtin_nontemporal_store(v3, dv + i + 3 * S);
+                    } else {
+                        dv[i] = v0;
+                        dv[i + S] = v1;
+                        dv[i + 2 * S] = v2;
+                        dv[i + 3 * S] = v3;
+                    }
+                }
+            }
+            for (; i < nv; i += S) {
+                const u32x4 v = __builtin_nontemporal_load(sv + i);
+                if (a.self_copy) reinterpret_cast<u32x4 *>(own + body)[i] = v;
+                for (int k = 1; k < a.n; ++k) {
+                    u32x4 *dv = reinterpret_cast<u32x4 *>(
+                        const_cast<char *>(a.peers.p[(a.rank + k) % a.n]) + at + body);
+                    if (NT) __builtin_nontemporal_store(v, dv + i);
+                    else dv[i] = v;
+                }
+            }
+            // the bytes before and after the vector body
+            const int64_t tail0 = body + nv * 16;
+            const int64_t nrest = head + (hi - tail0);
+            for (int64_t r = t; r < nrest; r += S) {
+                const int64_t b = r < head ? lo + r : tail0 + (r - head);
+                const char v = s[b];
+                if (a.self_copy) own[b] = v;
+                for (int k = 1; k < a.n; ++k)
+                    const_cast<char *>(a.peers.p[(a.rank + k) % a.n])[at + b] = v;
+            }
+        } else {
+            if (a.self_copy) pipe_copy(s, own, lo, hi, false);
+            for (int k = 1; k < a.n; ++k)
+                pipe_copy(s, const_cast<char *>(a.peers.p[(a.rank + k) % a.n]) + at, lo, hi, NT);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) sys_release();
+    __syncthreads();
+    __shared__ int gave_up;
+    if (t == 0) gave_up = 0;
+    __syncthreads();
+    if (t < a.n && t != a.rank) {
+        __hip_atomic_store(a.peer_flags.p[t] + g * kMaxRanks + a.rank, a.epoch, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!wait_epoch(a.flags + g * kMaxRanks + t, a.epoch, a.err, a.timeout_ticks,
+                        a.flags + kAbortWord))
+            gave_up = 1;
+    }
+    __syncthreads();
+    if (gave_up) return;  // a peer never arrived: its slot holds nothing of this call
+    acquire_once();
+    for (int p = 0; p < a.n; ++p) {
+        if (p == a.rank) continue;
+        a2a_slice(a.rcount[p], g, G, &lo, &hi);
+        pipe_copy(a.mine + (int64_t)p * a.slot + a.rphase[p], a.rbuf + a.rdispl[p], lo, hi, false);
+    }
+    if (a.mark) {  // the host-observed completion, by the last workgroup
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (t == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            if (__hip_atomic_fetch_add(a.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
+                (uint32_t)G - 1) {
+                __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.mark, a.mark_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launch rows
 using red_launch_fn = hipError_t (*)(dim3, const ptr_set &, const ptr_set &, int, int, int, int,
                                      const red_jobs &, hipStream_t);

@@ -86,5 +86,24 @@ inline size_t alltoall_fit_chunk(int n, size_t avail) {
     const size_t per = (avail / (size_t)n) & ~(size_t)255;
     return per < 512 ? 0 : per - 256;
 }
+// allgatherv / gather(v) / scatter(v) ride the alltoall's exchange.  `slots`
+// says how many senders store into one rank's landing buffer in a pass: all
+// n for allgatherv and gather(v) (slot [p] holds rank p's block), ONE for
+// scatter(v) (only the root stores, into slot [0]).  need = slots * slot.
+inline land_layout exchange_landing(int slots, size_t chunk, size_t M) {
+    return alltoall_landing(slots, chunk, M);
+}
+inline int allgatherv_slots(int n) { return n; }
+inline int gather_slots(int n) { return n; }
+inline int scatter_slots(int /*n*/) { return 1; }
+inline land_layout allgatherv_landing(int n, size_t chunk, size_t M) {
+    return exchange_landing(allgatherv_slots(n), chunk, M);
+}
+inline land_layout gather_landing(int n, size_t chunk, size_t M) {
+    return exchange_landing(gather_slots(n), chunk, M);
+}
+inline land_layout scatter_landing(int n, size_t chunk, size_t M) {
+    return exchange_landing(scatter_slots(n), chunk, M);
+}
 
 }  // namespace ompi_amd

@@ -224,6 +224,42 @@ int mca_coll_rocm_alltoallv_init(const void *sbuf, const int *scounts, const int
                                  ompi_request_t **request, mca_coll_base_module_t *module);
 #endif
 
+/* MPI_Allgatherv, MPI_Gather, MPI_Gatherv, MPI_Scatter, MPI_Scatterv, each
+ * blocking, nonblocking and persistent: fifteen slots.  As above, a harness
+ * build compiles them only with HARNESS_COLL_GATHER (and a stand-in coll.h
+ * that has the slots first on its include path). */
+#if !defined(HARNESS_COLL) || defined(HARNESS_COLL_GATHER)
+#define ROCM_HAVE_GATHER 1
+#define ROCM_GATHER_SLOTS(X)                                                                 \
+    X(allgatherv) X(iallgatherv) X(allgatherv_init) X(gather) X(igather) X(gather_init)       \
+    X(gatherv) X(igatherv) X(gatherv_init) X(scatter) X(iscatter) X(scatter_init)            \
+    X(scatterv) X(iscatterv) X(scatterv_init)
+#define ROCM_AGV_PARAMS                                                                      \
+    const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts, \
+        const int *disps, struct ompi_datatype_t *rdtype
+#define ROCM_ROOTED_PARAMS                                                                   \
+    const void *sbuf, int scount, struct ompi_datatype_t *sdtype, void *rbuf, int rcount,     \
+        struct ompi_datatype_t *rdtype, int root
+#define ROCM_GATHERV_PARAMS ROCM_AGV_PARAMS, int root
+#define ROCM_SCATTERV_PARAMS                                                                 \
+    const void *sbuf, const int *scounts, const int *disps, struct ompi_datatype_t *sdtype,   \
+        void *rbuf, int rcount, struct ompi_datatype_t *rdtype, int root
+/* the three forms of one collective */
+#define ROCM_DECLARE_FORMS(name, PARAMS)                                                     \
+    int mca_coll_rocm_##name(PARAMS, struct ompi_communicator_t *comm,                        \
+                             mca_coll_base_module_t *module);                                \
+    int mca_coll_rocm_i##name(PARAMS, struct ompi_communicator_t *comm,                       \
+                              ompi_request_t **request, mca_coll_base_module_t *module);     \
+    int mca_coll_rocm_##name##_init(PARAMS, struct ompi_communicator_t *comm,                 \
+                                    struct ompi_info_t *info, ompi_request_t **request,      \
+                                    mca_coll_base_module_t *module);
+ROCM_DECLARE_FORMS(allgatherv, ROCM_AGV_PARAMS)
+ROCM_DECLARE_FORMS(gather, ROCM_ROOTED_PARAMS)
+ROCM_DECLARE_FORMS(scatter, ROCM_ROOTED_PARAMS)
+ROCM_DECLARE_FORMS(gatherv, ROCM_GATHERV_PARAMS)
+ROCM_DECLARE_FORMS(scatterv, ROCM_SCATTERV_PARAMS)
+#endif
+
 END_C_DECLS
 
 #endif /* MCA_COLL_ROCM_EXPORT_H */

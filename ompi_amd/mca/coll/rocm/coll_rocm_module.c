@@ -303,6 +303,11 @@ static void rocm_module_destruct(mca_coll_rocm_module_t *m)
     if (NULL != m->c_coll.coll_alltoallv_init_module)
         OBJ_RELEASE(m->c_coll.coll_alltoallv_init_module);
 #endif
+#ifdef ROCM_HAVE_GATHER
+#define DROP(fn) if (NULL != m->c_coll.coll_##fn##_module) OBJ_RELEASE(m->c_coll.coll_##fn##_module);
+    ROCM_GATHER_SLOTS(DROP)
+#undef DROP
+#endif
     if (NULL != m->dev_comm) (void) ompi_amd_comm_destroy(m->dev_comm);
     for (int k = 0; k < 2; ++k) {
         (void) ompi_amd_device_free(m->dstage[k]);
@@ -363,6 +368,11 @@ mca_coll_base_module_t *mca_coll_rocm_comm_query(struct ompi_communicator_t *com
     m->super.coll_alltoall_init = mca_coll_rocm_alltoall_init;
     m->super.coll_alltoallv_init = mca_coll_rocm_alltoallv_init;
 #endif
+#ifdef ROCM_HAVE_GATHER
+#define OFFER(fn) m->super.coll_##fn = mca_coll_rocm_##fn;
+    ROCM_GATHER_SLOTS(OFFER)
+#undef OFFER
+#endif
     return &m->super;
 }
 
@@ -410,6 +420,11 @@ int mca_coll_rocm_module_enable(mca_coll_base_module_t *module, struct ompi_comm
     SAVE(ialltoallv);
     SAVE(alltoall_init);
     SAVE(alltoallv_init);
+#endif
+#ifdef ROCM_HAVE_GATHER
+#define SAVE_ONE(fn) SAVE(fn);
+    ROCM_GATHER_SLOTS(SAVE_ONE)
+#undef SAVE_ONE
 #endif
 #undef SAVE
 
@@ -1793,7 +1808,10 @@ static int rocm_alltoall_common(const void *sbuf, int scount, struct ompi_dataty
     return rocm_wrap_plan(rc, plan, st, comm, request);
 }
 
-/* elements an alltoallv operand spans */
+#endif /* ROCM_HAVE_ALLTOALL */
+
+#if defined(ROCM_HAVE_ALLTOALL) || defined(ROCM_HAVE_GATHER)
+/* elements a vector operand (counts / displacements) spans */
 static size_t a2av_span(const int *counts, const int *disps, int n)
 {
     size_t span = 0;
@@ -1817,6 +1835,9 @@ static void a2av_bytes(const rocm_operand_t *x, struct ompi_datatype_t *dtype, c
         bd[p] = (size_t) disps[p] * (2 == x->how ? size : (size_t) ext);
     }
 }
+#endif
+
+#ifdef ROCM_HAVE_ALLTOALL
 
 static int rocm_alltoallv_common(const void *sbuf, const int *scounts, const int *sdisps,
                                  struct ompi_datatype_t *sdtype, void *rbuf, const int *rcounts,
@@ -1931,3 +1952,238 @@ int mca_coll_rocm_alltoallv_init(const void *sbuf, const int *scounts, const int
                                  info, request, (mca_coll_rocm_module_t *) module, A2A_PERSISTENT);
 }
 #endif /* ROCM_HAVE_ALLTOALL */
+
+#ifdef ROCM_HAVE_GATHER
+/* --------------------------------------- allgatherv / gather(v) / scatter(v)
+ * MPI_Allgatherv, MPI_Gather, MPI_Gatherv, MPI_Scatter, MPI_Scatterv and
+ * their nonblocking and persistent forms (fifteen slots), in
+ * rocm_alltoall_common's shape: they move bytes, so any datatype qualifies;
+ * the vote covers residency and layout, and only the buffers significant at
+ * a rank vote there (a non-root's rbuf of a gather is not looked at, and is
+ * handed on as NULL); a significant operand whose layout is not contiguous is
+ * packed when the device path runs.  The library takes bytes: counts are
+ * count * type size, displacements disp * extent (disp * type size inside a
+ * packed operand).  coll_rocm_max_device_mib bounds what every rank computes
+ * alike: allgatherv's largest rcount and gather's / scatter's bytes per rank;
+ * gatherv / scatterv have no such size (a non-root sees its own count) and
+ * need none.  One helper per shape — allgatherv, uniform rooted, vector
+ * rooted — and form: 0 blocking, 1 nonblocking, 2 persistent. */
+enum { XCH_BLOCKING = 0, XCH_NONBLOCKING = 1, XCH_PERSISTENT = 2 };
+
+/* the saved function / the library call of collective X in the call's form */
+#define XCH_SAVED(X, ...)                                                                      \
+    (XCH_BLOCKING == form                                                                      \
+         ? m->c_coll.coll_##X(__VA_ARGS__, comm, m->c_coll.coll_##X##_module)                  \
+         : XCH_NONBLOCKING == form                                                             \
+               ? m->c_coll.coll_i##X(__VA_ARGS__, comm, &x.inner, m->c_coll.coll_i##X##_module) \
+               : m->c_coll.coll_##X##_init(__VA_ARGS__, comm, info, &x.inner,                  \
+                                           m->c_coll.coll_##X##_init_module))
+#define XCH_DEVICE(X, ...)                                                                     \
+    (XCH_BLOCKING == form      ? ompi_amd_##X(m->dev_comm, __VA_ARGS__, NULL)                  \
+     : XCH_NONBLOCKING == form ? ompi_amd_i##X(m->dev_comm, __VA_ARGS__, NULL, &x.nb)          \
+                               : ompi_amd_##X##_init(m->dev_comm, __VA_ARGS__, &x.plan))
+
+struct rocm_xch {
+    rocm_operand_t o[2];
+    struct rocm_nb_stage *st;
+    ompi_amd_request_t *nb;
+    ompi_amd_plan_t *plan;
+    ompi_request_t *inner;
+    int path;
+};
+
+static int rocm_xch_begin(mca_coll_rocm_module_t *m, int form, int uniform_ok, int local_ok,
+                          struct rocm_xch *x)
+{
+    x->st = NULL;
+    x->nb = NULL;
+    x->plan = NULL;
+    x->inner = NULL;
+    if (XCH_BLOCKING == form) return rocm_begin(m, uniform_ok, local_ok, x->o, 2, &x->path);
+    return rocm_nb_begin(m, uniform_ok, local_ok, x->o, 2, &x->st, &x->path);
+}
+
+/* what follows the saved function's / the library's return in each form */
+static int rocm_xch_end(mca_coll_rocm_module_t *m, int form, int rc, struct rocm_xch *x,
+                        struct ompi_communicator_t *comm, ompi_request_t **request)
+{
+    if (ROCM_DEVICE != x->path) {
+        if (XCH_BLOCKING == form) return rocm_unstage(m, x->o, 2, rc);
+        return rocm_saved_post(rc, x->inner, x->st, comm, request);
+    }
+    if (XCH_BLOCKING == form) return rocm_dev_finish(m, x->o, 2, rc);
+    if (XCH_NONBLOCKING == form) return rocm_nb_post(rc, x->nb, x->st, comm, request);
+    return rocm_wrap_plan(rc, x->plan, x->st, comm, request);
+}
+
+/* a significant operand of `elems` elements is device memory in one piece */
+static int xch_operand_ok(const void *buf, struct ompi_datatype_t *dtype, size_t elems)
+{
+    return 0 == elems || (dev(buf) && ompi_datatype_is_contiguous_memory_layout(dtype, (int) elems));
+}
+
+static size_t xch_type_size(struct ompi_datatype_t *dtype)
+{
+    size_t size = 0;
+    (void) ompi_datatype_type_size(dtype, &size);
+    return size;
+}
+
+static int rocm_allgatherv_common(ROCM_AGV_PARAMS, struct ompi_communicator_t *comm,
+                                  struct ompi_info_t *info, ompi_request_t **request,
+                                  mca_coll_rocm_module_t *m, int form)
+{
+    const int inplace = MPI_IN_PLACE == sbuf;
+    const int n = ompi_comm_size(comm);
+    const size_t rspan = a2av_span(rcounts, disps, n);
+    const size_t rsize = xch_type_size(rdtype);
+    /* the receive side is read too: what lies between its blocks survives a
+     * staged copy back */
+    struct rocm_xch x = {{{(void *) sbuf, inplace ? 0 : (size_t) scount, sdtype, 1, 0},
+                          {rbuf, rspan, rdtype, 1, 1}}, NULL, NULL, NULL, NULL, 0};
+    size_t rc_[OMPI_AMD_MAX_RANKS], rd[OMPI_AMD_MAX_RANKS], most = 0;
+    int rc;
+    for (int p = 0; p < n; ++p)
+        if ((size_t) rcounts[p] * rsize > most) most = (size_t) rcounts[p] * rsize;
+    rc = rocm_xch_begin(m, form, bytes_ok(most),
+                        xch_operand_ok(rbuf, rdtype, rspan) &&
+                            (inplace || xch_operand_ok(sbuf, sdtype, (size_t) scount)), &x);
+    if (OMPI_SUCCESS != rc) return rc;
+    if (ROCM_DEVICE != x.path) {
+        rc = XCH_SAVED(allgatherv, x.o[0].use, scount, sdtype, x.o[1].use, rcounts, disps, rdtype);
+    } else {
+        a2av_bytes(&x.o[1], rdtype, rcounts, disps, n, rc_, rd);
+        sbuf = inplace ? (const void *) 1 : x.o[0].use;
+        rc = XCH_DEVICE(allgatherv, sbuf, inplace ? 0 : (size_t) scount * xch_type_size(sdtype),
+                        x.o[1].use, rc_, rd);
+    }
+    return rocm_xch_end(m, form, rc, &x, comm, request);
+}
+
+/* gather / scatter: one count.  The root's side of n blocks is the `wide`
+ * operand, every rank's single block the `narrow` one; MPI_IN_PLACE stands
+ * in the root's narrow operand. */
+static int rocm_rooted_common(int scatter, ROCM_ROOTED_PARAMS, struct ompi_communicator_t *comm,
+                              struct ompi_info_t *info, ompi_request_t **request,
+                              mca_coll_rocm_module_t *m, int form)
+{
+    const int is_root = ompi_comm_rank(comm) == root;
+    const size_t n = (size_t) ompi_comm_size(comm);
+    const int inplace = is_root && MPI_IN_PLACE == (scatter ? (const void *) rbuf : sbuf);
+    /* elements of each operand that count at this rank */
+    const size_t selems = scatter ? (is_root ? (size_t) scount * n : 0) : (inplace ? 0 : (size_t) scount);
+    const size_t relems = scatter ? (inplace ? 0 : (size_t) rcount) : (is_root ? (size_t) rcount * n : 0);
+    struct rocm_xch x = {{{selems || inplace ? (void *) sbuf : NULL, selems, sdtype, 1, 0},
+                          {relems || inplace ? rbuf : NULL, relems, rdtype, !scatter && inplace, 1}},
+                         NULL, NULL, NULL, NULL, 0};
+    /* bytes per rank, from the side that is significant here (matching type
+     * signatures make them equal on every rank, MPI-4.1 §6.4) */
+    const size_t bytes = (scatter ? !is_root : is_root) ? (size_t) rcount * xch_type_size(rdtype)
+                                                        : (size_t) scount * xch_type_size(sdtype);
+    const void *s;
+    void *r;
+    int rc = rocm_xch_begin(m, form, bytes_ok(bytes),
+                            xch_operand_ok(sbuf, sdtype, selems) && xch_operand_ok(rbuf, rdtype, relems),
+                            &x);
+    if (OMPI_SUCCESS != rc) return rc;
+    s = x.o[0].use;
+    r = x.o[1].use;
+    if (ROCM_DEVICE != x.path) {
+        rc = scatter ? XCH_SAVED(scatter, s, scount, sdtype, r, rcount, rdtype, root)
+                     : XCH_SAVED(gather, s, scount, sdtype, r, rcount, rdtype, root);
+    } else if (scatter) {
+        if (inplace) r = (void *) 1;
+        rc = XCH_DEVICE(scatter, s, r, bytes, root);
+    } else {
+        if (inplace) s = (const void *) 1;
+        rc = XCH_DEVICE(gather, s, r, bytes, root);
+    }
+    return rocm_xch_end(m, form, rc, &x, comm, request);
+}
+
+/* gatherv / scatterv: `counts` / `disps` describe the root's wide operand
+ * (significant only there), `count` every rank's narrow one. */
+static int rocm_rooted_v_common(int scatter, const void *sbuf, void *rbuf, int count,
+                                struct ompi_datatype_t *ndtype, const int *counts, const int *disps,
+                                struct ompi_datatype_t *wdtype, int root,
+                                struct ompi_communicator_t *comm, struct ompi_info_t *info,
+                                ompi_request_t **request, mca_coll_rocm_module_t *m, int form)
+{
+    const int is_root = ompi_comm_rank(comm) == root;
+    const int n = ompi_comm_size(comm);
+    const int inplace = is_root && MPI_IN_PLACE == (scatter ? (const void *) rbuf : sbuf);
+    const size_t span = is_root ? a2av_span(counts, disps, n) : 0;
+    const size_t nelems = inplace ? 0 : (size_t) count;
+    /* o[0] the send side, o[1] the receive side; the gatherv root's receive
+     * side is read too (its gaps survive a staged copy back) */
+    struct rocm_xch x = {{{scatter ? (span ? (void *) sbuf : NULL) : (nelems || inplace ? (void *) sbuf : NULL),
+                           scatter ? span : nelems, scatter ? wdtype : ndtype, 1, 0},
+                          {scatter ? (nelems || inplace ? rbuf : NULL) : (span ? rbuf : NULL),
+                           scatter ? nelems : span, scatter ? ndtype : wdtype, !scatter, 1}},
+                         NULL, NULL, NULL, NULL, 0};
+    size_t bc[OMPI_AMD_MAX_RANKS], bd[OMPI_AMD_MAX_RANKS];
+    const size_t nbytes = nelems * xch_type_size(ndtype);
+    const void *s;
+    void *r;
+    int rc = rocm_xch_begin(m, form, 1,
+                            xch_operand_ok(scatter ? rbuf : (void *) sbuf, ndtype, nelems) &&
+                                xch_operand_ok(scatter ? (void *) sbuf : rbuf, wdtype, span),
+                            &x);
+    if (OMPI_SUCCESS != rc) return rc;
+    s = x.o[0].use;
+    r = x.o[1].use;
+    if (ROCM_DEVICE != x.path) {
+        rc = scatter ? XCH_SAVED(scatterv, s, counts, disps, wdtype, r, count, ndtype, root)
+                     : XCH_SAVED(gatherv, s, count, ndtype, r, counts, disps, wdtype, root);
+        return rocm_xch_end(m, form, rc, &x, comm, request);
+    }
+    if (is_root) a2av_bytes(&x.o[scatter ? 0 : 1], wdtype, counts, disps, n, bc, bd);
+    if (scatter) {
+        if (inplace) r = (void *) 1;
+        rc = XCH_DEVICE(scatterv, s, is_root ? bc : NULL, is_root ? bd : NULL, r, nbytes, root);
+    } else {
+        if (inplace) s = (const void *) 1;
+        rc = XCH_DEVICE(gatherv, s, nbytes, r, is_root ? bc : NULL, is_root ? bd : NULL, root);
+    }
+    return rocm_xch_end(m, form, rc, &x, comm, request);
+}
+
+/* the three slots of one collective: CALL gets info, request and form */
+#define ROCM_DEFINE_FORMS(name, PARAMS, CALL)                                                \
+    int mca_coll_rocm_##name(PARAMS, struct ompi_communicator_t *comm,                        \
+                             mca_coll_base_module_t *module)                                 \
+    {                                                                                        \
+        struct ompi_info_t *info = NULL;                                                     \
+        ompi_request_t **request = NULL;                                                     \
+        const int form = XCH_BLOCKING;                                                       \
+        return CALL;                                                                         \
+    }                                                                                        \
+    int mca_coll_rocm_i##name(PARAMS, struct ompi_communicator_t *comm,                       \
+                              ompi_request_t **request, mca_coll_base_module_t *module)      \
+    {                                                                                        \
+        struct ompi_info_t *info = NULL;                                                     \
+        const int form = XCH_NONBLOCKING;                                                    \
+        return CALL;                                                                         \
+    }                                                                                        \
+    int mca_coll_rocm_##name##_init(PARAMS, struct ompi_communicator_t *comm,                 \
+                                    struct ompi_info_t *info, ompi_request_t **request,      \
+                                    mca_coll_base_module_t *module)                          \
+    {                                                                                        \
+        const int form = XCH_PERSISTENT;                                                     \
+        return CALL;                                                                         \
+    }
+#define XCH_TAIL comm, info, request, (mca_coll_rocm_module_t *) module, form
+
+ROCM_DEFINE_FORMS(allgatherv, ROCM_AGV_PARAMS,
+                  rocm_allgatherv_common(sbuf, scount, sdtype, rbuf, rcounts, disps, rdtype, XCH_TAIL))
+ROCM_DEFINE_FORMS(gather, ROCM_ROOTED_PARAMS,
+                  rocm_rooted_common(0, sbuf, scount, sdtype, rbuf, rcount, rdtype, root, XCH_TAIL))
+ROCM_DEFINE_FORMS(scatter, ROCM_ROOTED_PARAMS,
+                  rocm_rooted_common(1, sbuf, scount, sdtype, rbuf, rcount, rdtype, root, XCH_TAIL))
+ROCM_DEFINE_FORMS(gatherv, ROCM_GATHERV_PARAMS,
+                  rocm_rooted_v_common(0, sbuf, rbuf, scount, sdtype, rcounts, disps, rdtype, root,
+                                       XCH_TAIL))
+ROCM_DEFINE_FORMS(scatterv, ROCM_SCATTERV_PARAMS,
+                  rocm_rooted_v_common(1, sbuf, rbuf, rcount, rdtype, scounts, disps, sdtype, root,
+                                       XCH_TAIL))
+#endif /* ROCM_HAVE_GATHER */
