@@ -169,6 +169,42 @@ int ompi_amd_coll_reduce_order(int size, size_t msg_bytes, size_t count, int roo
  * leaves those reductions to coll/tuned.  Host-only. */
 int ompi_amd_coll_reduce_order_forced(int size, size_t msg_bytes, size_t count, int root,
                                       int root_inplace, int forced, int *order, int *first);
+/* The fold of one collective over `size` (1..16) buffers of the calling
+ * process, for tests: no communicator, no IPC, no flag — the ranks' inputs
+ * are srcs[0 .. size), and the reduce kernel is planned and launched exactly
+ * as the entry point of that collective does it on rank `which`, so a result
+ * is what that rank would hold.  Every dsts[0 .. ndst) (1 <= ndst <= size)
+ * receives it, as the fused push stores a block into every rank's rbuf.
+ *   kind ALLREDUCE: counts[0] elements, alg = coll_tuned_allreduce_algorithm
+ *     (0..6), inplace = rank 0 passed MPI_IN_PLACE (non-overlapping only),
+ *     red_alg = coll_tuned_reduce_algorithm (0, 1, 3, 4, 5).  which = -1 folds
+ *     the whole vector into dst[0, count); which = b only ring block b
+ *     (ompi_amd_coll_block), in place in the vector, the rest of dst untouched.
+ *   kind REDUCE: which = root, inplace = the root passed MPI_IN_PLACE, red_alg.
+ *   kind REDUCE_SCATTER: counts[0 .. size) = rcounts, alg =
+ *     coll_tuned_reduce_scatter_algorithm (0 fixed, 1 non-overlapping, 2
+ *     halving, 3 ring), red_alg and inplace for non-overlapping; block `which`
+ *     goes to dst[0, rcounts[which]).
+ *   kind REDUCE_SCATTER_BLOCK: counts[0] = rcount, red_alg, block `which`.
+ *   kind SCAN / EXSCAN: counts[0] elements at rank `which` (exscan at rank 0
+ *     stores nothing).
+ * max_blocks caps the grid (0: the communicators' default "blocks");
+ * nt_store != 0 stores non-temporally (param "copy_nt").  size == 1 is a copy.
+ * Returns before any device call: OMPI_AMD_ERR_BAD_PARAM for a kind, size,
+ * ndst, which or allreduce alg out of range, a NULL counts, and a NULL
+ * pointer among those read or written when the count is not 0;
+ * OMPI_AMD_ERR_UNSUPPORTED for an (op, type) without a handler or an
+ * algorithm number the device path does not run; success for a zero count.
+ * Stream-ordered. */
+#define OMPI_AMD_FOLD_ALLREDUCE 0
+#define OMPI_AMD_FOLD_REDUCE 1
+#define OMPI_AMD_FOLD_REDUCE_SCATTER 2
+#define OMPI_AMD_FOLD_REDUCE_SCATTER_BLOCK 3
+#define OMPI_AMD_FOLD_SCAN 4
+#define OMPI_AMD_FOLD_EXSCAN 5
+int ompi_amd_coll_fold_local(int kind, int size, const void *const *srcs, void *const *dsts,
+                             int ndst, const size_t *counts, int type, int op, int alg, int red_alg,
+                             int which, int inplace, int max_blocks, int nt_store, void *stream);
 
 /* MPI_IN_PLACE is spelled sbuf == rbuf or sbuf == (void *)1.
  * Stream-ordered: results are valid when `stream` reaches this point; the

@@ -151,6 +151,10 @@ PROTOTYPES = [
     ("ompi_amd_coll_reduce_order_forced", _C.c_int,
      [_C.c_int, _C.c_size_t, _C.c_size_t, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int),
       _C.POINTER(_C.c_int)]),
+    ("ompi_amd_coll_fold_local", _C.c_int,
+     [_C.c_int, _C.c_int, _C.POINTER(_C.c_void_p), _C.POINTER(_C.c_void_p), _C.c_int,
+      _C.POINTER(_C.c_size_t), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int,
+      _C.c_int, _C.c_void_p]),
     ("ompi_amd_allreduce", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_void_p]),
     ("ompi_amd_allreduce_init", _C.c_int,

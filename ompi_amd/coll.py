@@ -559,3 +559,26 @@ def block_owner(nranks: int, block: int) -> int:
     """Rank that produces ring block `block` (the rank where the
     reference's ring finishes it: block - 1 mod N)."""
     return _lib.load().ompi_amd_coll_owner(nranks, block)
+
+
+(FOLD_ALLREDUCE, FOLD_REDUCE, FOLD_REDUCE_SCATTER, FOLD_REDUCE_SCATTER_BLOCK, FOLD_SCAN,
+ FOLD_EXSCAN) = range(6)
+
+
+def fold_local(kind: int, srcs, dsts, counts, dtype: Datatype, op: Op, *, alg: int = 0,
+               red_alg: int = 0, which: int = 0, inplace: bool = False, max_blocks: int = 0,
+               nt_store: bool = True, stream=None) -> None:
+    """ompi_amd_coll_fold_local: the fold of collective `kind` over the
+    len(srcs) buffers of this process (the ranks' inputs: device tensors or
+    pointers), planned and launched as rank `which` of such a communicator
+    would, stored to every buffer of dsts.  counts: an element count, or the
+    rcounts list of FOLD_REDUCE_SCATTER.  No communicator, no peer, no flag
+    (tests; include/ompi_amd_coll.h).  Stream-ordered."""
+    n = len(srcs)
+    sp = (ctypes.c_void_p * n)(*[_ptr(s) for s in srcs])
+    dp = (ctypes.c_void_p * len(dsts))(*[_ptr(d) for d in dsts])
+    cs = list(counts) if isinstance(counts, (list, tuple)) else [counts]
+    cv = (ctypes.c_size_t * len(cs))(*cs)
+    _lib.check(_lib.load().ompi_amd_coll_fold_local(
+        kind, n, sp, dp, len(dsts), cv, dtype.code, op.index, alg, red_alg, which,
+        1 if inplace else 0, max_blocks, 1 if nt_store else 0, _stream(stream)), "coll_fold_local")

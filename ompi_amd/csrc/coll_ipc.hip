@@ -271,6 +271,7 @@ static int64_t block_cnt(int64_t b, int64_t split, int64_t early, int64_t late) 
 // The operand order of coll/tuned's reduce for a commutative op
 // (coll_tuned_decision_fixed.c:354-428; msg = type size * count).
 struct red_order { int order, first, flags; };
+constexpr int kDefaultMaxBlocks = 1024;  // grid cap of the transfer kernels
 // forced: coll_tuned_reduce_algorithm under coll_tuned_use_dynamic_rules
 // (coll_tuned_reduce_decision.c:146-179) — 1 basic_linear, 3 pipeline,
 // 4 binary, 5 binomial; segmentation does not change an element's operand
@@ -604,7 +605,7 @@ struct ompi_amd_comm {
     size_t fused_bytes = 64 << 10;
     int zero_copy = 1;
     int64_t timeout_ms = 30000;
-    int max_blocks = 1024;
+    int max_blocks = kDefaultMaxBlocks;  // param "blocks"
     // pipelined schemes: every workgroup of the grid runs pipe_passes
     // slices of each block (param "pipe_passes"), none under pipe_slice
     // bytes (param "pipe_slice"; smaller messages use fewer workgroups);
@@ -1991,13 +1992,15 @@ static ptr_set push_order(const ompi_amd_comm_t *c, const ptr_set &bufs) {
 
 // Reduce `nsrc` sources (ranks 0..nsrc of src) in `order`, store to the
 // ndst buffers of dst.
-static int launch_reduce(ompi_amd_comm_t *c, int op, int type, const ptr_set &src, int nsrc,
-                         const ptr_set &dst, int ndst, int order, int flags, red_jobs jobs,
-                         hipStream_t s) {
+// The communicator-free core (ompi_amd_coll_fold_local launches through it
+// too): each job's head / common-phase detection, the grid from max_blocks
+// over the jobs, the store kind.
+static int launch_reduce_core(int op, int type, const ptr_set &src, int nsrc, const ptr_set &dst,
+                              int ndst, int order, int flags, red_jobs jobs, int max_blocks,
+                              bool nt_store, hipStream_t s) {
     red_launch_fn f = red_fn(op, type);
     if (!f) return OMPI_AMD_ERR_UNSUPPORTED;
     if (jobs.n == 0 || nsrc < 1) return OMPI_AMD_SUCCESS;
-    note_stream(c, s);
     const size_t ext = ompi_amd_type_extent(type);
     int64_t most = 0;
     for (int i = 0; i < jobs.n; ++i) {
@@ -2017,10 +2020,20 @@ static int launch_reduce(ompi_amd_comm_t *c, int op, int type, const ptr_set &sr
     if (most == 0) return OMPI_AMD_SUCCESS;
     const int64_t per = (int64_t)(16 / ext) * kXferThreads;
     int64_t blocks = (most + per - 1) / per;
-    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, std::max(1, c->max_blocks / jobs.n)));
+    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, std::max(1, max_blocks / jobs.n)));
     return record_hip(f(dim3((unsigned)blocks, (unsigned)jobs.n), src, dst, ndst, nsrc, order,
-                        flags | (c->copy_nt ? FOLD_NT_STORE : 0), jobs, s),
+                        flags | (nt_store ? FOLD_NT_STORE : 0), jobs, s),
                       "reduce launch");
+}
+
+static int launch_reduce(ompi_amd_comm_t *c, int op, int type, const ptr_set &src, int nsrc,
+                         const ptr_set &dst, int ndst, int order, int flags, const red_jobs &jobs,
+                         hipStream_t s) {
+    if (!red_fn(op, type)) return OMPI_AMD_ERR_UNSUPPORTED;
+    if (jobs.n == 0 || nsrc < 1) return OMPI_AMD_SUCCESS;
+    note_stream(c, s);
+    return launch_reduce_core(op, type, src, nsrc, dst, ndst, order, flags, jobs, c->max_blocks,
+                              c->copy_nt != 0, s);
 }
 
 // Bracket one phase launch with timing events when profiling.
@@ -2174,6 +2187,17 @@ static void fold_jobs(const fold_plan &p, int64_t count, int n, int block, red_j
         j.aux = o << 8;
     }
 }
+
+// The single job of reduce, reduce_scatter(_block) and scan: elements
+// [off, off + cnt) of every source, stored at off_dst, virtual rank 0 = first.
+static red_jobs one_job(int64_t off, int64_t cnt, int64_t off_dst, int first) {
+    red_jobs jobs;
+    jobs.n = 1;
+    jobs.j[0] = {off, cnt, off_dst, first, -1};
+    return jobs;
+}
+// scan / exscan at `rank`: the ring fold at first = 0 over this many sources
+static int scan_sources(int rank, bool exclusive) { return exclusive ? rank : rank + 1; }
 
 static int stage_in(ompi_amd_comm_t *c, const void *src, size_t bytes, stage_half *sh,
                     hipStream_t s) {
@@ -2617,9 +2641,7 @@ static int reduce_my_block(ompi_amd_comm_t *c, const void *src, void *rbuf, size
                            int64_t off, int64_t cnt, int64_t max_cnt, int op, int type,
                            red_order ro, bool inplace, hipStream_t s,
                            const size_t *rcounts = nullptr) {
-    red_jobs jobs;
-    jobs.n = 1;
-    jobs.j[0] = {off, cnt, 0, ro.first, -1};
+    red_jobs jobs = one_job(off, cnt, 0, ro.first);
     const int n = c->size;
     const size_t ext = ompi_amd_type_extent(type);
     if (!lands(c, total_bytes)) {
@@ -2744,10 +2766,8 @@ static int scan_common(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
     const size_t bytes = count * ompi_amd_type_extent(type);
     const bool inplace = in_place(sbuf, rbuf);
     const void *src = inplace ? rbuf : sbuf;
-    const int nsrc = exclusive ? c->rank : c->rank + 1;
-    red_jobs jobs;
-    jobs.n = 1;
-    jobs.j[0] = {0, (int64_t)count, 0, 0, -1};
+    const int nsrc = scan_sources(c->rank, exclusive);
+    const red_jobs jobs = one_job(0, (int64_t)count, 0, 0);
     if (c->size == 1) {
         if (exclusive || inplace) return OMPI_AMD_SUCCESS;
         return record_hip(hipMemcpyAsync(rbuf, src, bytes, hipMemcpyDeviceToDevice, s), "copy");
@@ -4103,8 +4123,7 @@ static int reduce_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t 
         stage_half sh;
         TRY(stage_in(c, src, bytes, &sh, s));
         if (c->rank != root) return OMPI_AMD_SUCCESS;
-        jobs.n = 1;
-        jobs.j[0] = {0, (int64_t)count, 0, ro.first, -1};
+        jobs = one_job(0, (int64_t)count, 0, ro.first);
         return launch_reduce(c, op, type, sh.peers, n, one_ptr(rbuf), 1, ro.order, ro.flags, jobs, s);
     }
     int64_t split, early, late;
@@ -4187,6 +4206,13 @@ int ompi_amd_reduce_scatter_block(ompi_amd_comm_t *c, const void *sbuf, void *rb
     return rsb_impl(c, inplace ? rbuf : sbuf, rbuf, rcount, type, op, inplace, comm_stream(c, stream));
 }
 
+// basic_linear rsb = tuned reduce of the whole vector to rank 0 (never
+// in place at that level) + scatter: every block folds in that order
+static red_order rsb_order(int n, size_t rcount, int type, int red_alg) {
+    const size_t tcount = rcount * (size_t)n;
+    return tuned_reduce_order(n, type_size(type) * tcount, tcount, 0, false, red_alg);
+}
+
 // src: the input (rbuf itself in place, n * rcount elements)
 static int rsb_impl(ompi_amd_comm_t *c, const void *src, void *rbuf, size_t rcount, int type,
                     int op, bool inplace, hipStream_t s) {
@@ -4199,10 +4225,7 @@ static int rsb_impl(ompi_amd_comm_t *c, const void *src, void *rbuf, size_t rcou
         if (inplace || src == rbuf) return OMPI_AMD_SUCCESS;
         return record_hip(hipMemcpyAsync(rbuf, src, rcount * ext, hipMemcpyDeviceToDevice, s), "copy");
     }
-    // basic_linear rsb = tuned reduce of the whole vector to rank 0 (never
-    // in place at that level) + scatter: my block folds in that order
-    const size_t tcount = rcount * (size_t)n;
-    const red_order ro = tuned_reduce_order(n, type_size(type) * tcount, tcount, 0, false, c->tuned_red_alg);
+    const red_order ro = rsb_order(n, rcount, type, c->tuned_red_alg);
     return reduce_my_block(c, src, rbuf, total, (int64_t)(rcount * (size_t)c->rank),
                            (int64_t)rcount, (int64_t)rcount, op, type, ro, inplace, s);
 }
@@ -4230,6 +4253,15 @@ static red_order tuned_reduce_scatter_order(int n, size_t total_bytes, int block
     }
     // ring: block b starts at rank b+1 and ends at b (coll_base_reduce_scatter.c:551-605)
     return {ORDER_RING, (block + 1) % n, 0};
+}
+
+// The order block `block` of a `total`-element reduce_scatter folds in:
+// non-overlapping is coll/tuned's reduce to rank 0, else the decision above.
+static red_order rs_order(int n, size_t total, int type, int block, bool inplace, int rs_alg,
+                          int red_alg) {
+    return rs_alg == TUNED_RS_NONOVERLAPPING
+               ? tuned_reduce_order(n, type_size(type) * total, total, 0, inplace, red_alg)
+               : tuned_reduce_scatter_order(n, total * type_size(type), block, rs_alg);
 }
 
 int ompi_amd_reduce_scatter(ompi_amd_comm_t *c, const void *sbuf, void *rbuf,
@@ -4261,11 +4293,101 @@ static int rs_impl(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, const size_
         return record_hip(hipMemcpyAsync(rbuf, src, rcounts[0] * ext, hipMemcpyDeviceToDevice, s),
                           "copy");
     }
-    const red_order ro = c->tuned_rs_alg == TUNED_RS_NONOVERLAPPING
-                             ? tuned_reduce_order(n, type_size(type) * total, total, 0, inplace, c->tuned_red_alg)
-                             : tuned_reduce_scatter_order(n, total * type_size(type), c->rank, c->tuned_rs_alg);
+    const red_order ro = rs_order(n, total, type, c->rank, inplace, c->tuned_rs_alg, c->tuned_red_alg);
     return reduce_my_block(c, src, rbuf, total * ext, (int64_t)off, (int64_t)rcounts[c->rank],
                            (int64_t)maxc, op, type, ro, inplace, s, rcounts);
+}
+
+// The fold of one collective over `size` buffers of this process: the plan,
+// the jobs and the launch are the ones the entry points above build, with
+// the ranks' inputs as the sources and no communicator (ompi_amd_coll.h).
+int ompi_amd_coll_fold_local(int kind, int size, const void *const *srcs, void *const *dsts, int ndst,
+                             const size_t *counts, int type, int op, int alg, int red_alg, int which,
+                             int inplace, int max_blocks, int nt_store, void *stream) {
+    if (kind < OMPI_AMD_FOLD_ALLREDUCE || kind > OMPI_AMD_FOLD_EXSCAN || size < 1 ||
+        size > kMaxRanks || ndst < 1 || ndst > size || !counts || max_blocks < 0)
+        return OMPI_AMD_ERR_BAD_PARAM;
+    const bool whole = kind == OMPI_AMD_FOLD_ALLREDUCE;  // which: a ring block, or -1 for all
+    if (which < (whole ? -1 : 0) || which >= size) return OMPI_AMD_ERR_BAD_PARAM;
+    if (kind == OMPI_AMD_FOLD_ALLREDUCE && (alg < 0 || alg >= TUNED_AR_COUNT))
+        return OMPI_AMD_ERR_BAD_PARAM;
+    if (kind == OMPI_AMD_FOLD_REDUCE_SCATTER && (alg < 0 || alg > TUNED_RS_RING))
+        return OMPI_AMD_ERR_UNSUPPORTED;
+    if (!tuned_red_alg_ok(red_alg)) return OMPI_AMD_ERR_UNSUPPORTED;
+    if (!ompi_amd_op_supported(op, type)) return OMPI_AMD_ERR_UNSUPPORTED;
+    const int n = size;
+    int nsrc = n, order = ORDER_RING, flags = 0;
+    int64_t out_cnt;  // elements a destination receives (size 1: the copy)
+    red_jobs jobs;
+    jobs.n = 0;
+    switch (kind) {
+    case OMPI_AMD_FOLD_ALLREDUCE: {
+        const fold_plan fp = allreduce_fold(n, alg, counts[0], type, inplace != 0, red_alg);
+        fold_jobs(fp, (int64_t)counts[0], n, which, &jobs);
+        order = fp.order;
+        flags = fp.flags;
+        out_cnt = (int64_t)counts[0];
+        break;
+    }
+    case OMPI_AMD_FOLD_REDUCE: {
+        const red_order ro = tuned_reduce_order(n, type_size(type) * counts[0], counts[0], which,
+                                                inplace != 0, red_alg);
+        jobs = one_job(0, (int64_t)counts[0], 0, ro.first);
+        order = ro.order;
+        flags = ro.flags;
+        out_cnt = (int64_t)counts[0];
+        break;
+    }
+    case OMPI_AMD_FOLD_REDUCE_SCATTER: {
+        size_t total = 0, off = 0;
+        for (int p = 0; p < n; ++p) {
+            if (p < which) off += counts[p];
+            total += counts[p];
+        }
+        const red_order ro = rs_order(n, total, type, which, inplace != 0, alg, red_alg);
+        jobs = one_job((int64_t)off, (int64_t)counts[which], 0, ro.first);
+        order = ro.order;
+        flags = ro.flags;
+        out_cnt = (int64_t)counts[which];
+        break;
+    }
+    case OMPI_AMD_FOLD_REDUCE_SCATTER_BLOCK: {
+        const red_order ro = rsb_order(n, counts[0], type, red_alg);
+        jobs = one_job((int64_t)(counts[0] * (size_t)which), (int64_t)counts[0], 0, ro.first);
+        order = ro.order;
+        flags = ro.flags;
+        out_cnt = (int64_t)counts[0];
+        break;
+    }
+    default:
+        nsrc = scan_sources(which, kind == OMPI_AMD_FOLD_EXSCAN);
+        jobs = one_job(0, (int64_t)counts[0], 0, 0);
+        out_cnt = (int64_t)counts[0];
+        break;
+    }
+    if (out_cnt == 0 || nsrc < 1) return OMPI_AMD_SUCCESS;  // exscan's rank 0 receives nothing
+    if (!srcs || !dsts) return OMPI_AMD_ERR_BAD_PARAM;
+    ptr_set sp{}, dp{};
+    for (int r = 0; r < nsrc; ++r) {
+        if (!srcs[r]) return OMPI_AMD_ERR_BAD_PARAM;
+        sp.p[r] = (const char *)srcs[r];
+    }
+    for (int d = 0; d < ndst; ++d) {
+        if (!dsts[d]) return OMPI_AMD_ERR_BAD_PARAM;
+        dp.p[d] = (const char *)dsts[d];
+    }
+    hipStream_t s = as_stream(stream);
+    if (n == 1) {  // every collective of one rank is a copy of its block
+        const size_t ext = ompi_amd_type_extent(type);
+        const char *from = sp.p[0] + (size_t)jobs.j[0].off * ext;
+        for (int d = 0; d < ndst; ++d)
+            if (dp.p[d] != from)
+                TRY(record_hip(hipMemcpyAsync(const_cast<char *>(dp.p[d]), from, (size_t)out_cnt * ext,
+                                              hipMemcpyDeviceToDevice, s), "copy"));
+        return OMPI_AMD_SUCCESS;
+    }
+    return launch_reduce_core(op, type, sp, nsrc, dp, ndst, order, flags, jobs,
+                              max_blocks ? max_blocks : kDefaultMaxBlocks, nt_store != 0, s);
 }
 
 int ompi_amd_scan(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t count, int type,

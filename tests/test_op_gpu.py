@@ -322,3 +322,66 @@ def test_misaligned_operands(orc, op, dt):
             orc.op_2buff(op.index, dt.code, a, exp, n)
             got2 = from_dev(tb, do, n * ext).view(dt.np_dtype)
             assert same_bits(got2, exp, dt), (op.name, dt.name, n, offs, "2buff")
+
+
+@pytest.mark.parametrize("op,dt", MISALIGNED, ids=[f"{o.name}-{d.name}" for o, d in MISALIGNED])
+def test_grid_stride_trips_under_a_block_cap(orc, op, dt):
+    """With the grid capped at 1 and at 3 workgroups (op_max_blocks; no cap by
+    default, so the loops otherwise make one trip), every workgroup walks its
+    operands in a partial, an exact and many trips: sizes of one chunk + 1,
+    three trips of three chunks + 7, and 65536 + 13 elements (a chunk is
+    4 x 256 vectors of E elements).  Co-aligned operands take the vector
+    kernel, one operand displaced by an element the element kernel; 2- and
+    3-buffer, and 3-buffer with out aliasing in1 and aliasing in2 (every lane
+    loads all its operands of a trip before it stores).  Bit-exact against
+    the oracle, the bytes after the result unchanged."""
+    import os
+    lib = _lib.load()
+    ext = dt.extent
+    E = 16 // ext
+    restore = int(os.environ.get("OMPI_AMD_OP_MAX_BLOCKS", "0") or 0)
+    restore = restore if restore > 0 else 1 << 24
+    try:
+        for cap in (1, 3):
+            assert lib.ompi_amd_set_tuning(b"op_max_blocks", cap) == 0
+            for n in (4 * 256 * E + 1, 3 * 4 * 256 * E * 3 + 7, 65536 + 13):
+                a, b = gen(dt, n, 700 + n % 97), gen(dt, n, 800 + n % 89)
+                out0 = gen(dt, n + 8, 900)
+                tail = np.ascontiguousarray(out0[n:]).view(np.uint8)
+                exp3 = out0[:n].copy()
+                orc.op_3buff(op.index, dt.code, a, b, exp3, n)
+                exp2 = b.copy()
+                orc.op_2buff(op.index, dt.code, a, exp2, n)
+                a_g, b_g = np.concatenate([a, out0[n:]]), np.concatenate([b, out0[n:]])
+
+                def verify(t, off, exp, what):
+                    got = from_dev(t, off, (n + 8) * ext)
+                    assert same_bits(got[:n * ext].view(dt.np_dtype), exp, dt), \
+                        (op.name, dt.name, "cap", cap, n, what)
+                    assert np.array_equal(got[n * ext:], tail), ("guard bytes", cap, n, what)
+
+                for d in (0, ext):  # d = ext: one operand a whole element off the others
+                    kern = "vector" if d == 0 else "element"
+                    ta, pa = to_dev(a, d)
+                    tb, pb = to_dev(b)
+                    to, po = to_dev(out0)
+                    mop.reduce_local_3buff_async(pa, pb, po, n, dt, op)
+                    torch.cuda.synchronize()
+                    verify(to, 0, exp3, (kern, "3buff"))
+                    ta, pa = to_dev(a, d)
+                    tb, pb = to_dev(b_g)
+                    mop.reduce_local_async(pa, pb, n, dt, op)
+                    torch.cuda.synchronize()
+                    verify(tb, 0, exp2, (kern, "2buff"))
+                    ta, pa = to_dev(a_g)
+                    tb, pb = to_dev(b, d)
+                    mop.reduce_local_3buff_async(pa, pb, pa, n, dt, op)
+                    torch.cuda.synchronize()
+                    verify(ta, 0, exp3, (kern, "3buff, out is in1"))
+                    ta, pa = to_dev(a, d)
+                    tb, pb = to_dev(b_g)
+                    mop.reduce_local_3buff_async(pa, pb, pb, n, dt, op)
+                    torch.cuda.synchronize()
+                    verify(tb, 0, exp3, (kern, "3buff, out is in2"))
+    finally:
+        assert lib.ompi_amd_set_tuning(b"op_max_blocks", restore) == 0
