@@ -93,6 +93,32 @@ int ompi_amd_ddt_unpack_iov(const ompi_amd_ddt_t *ddt, size_t count,
                             ompi_amd_iovec_t *iov, uint32_t *out_size,
                             size_t *max_data, void *stream);
 
+/* Which kernel each convertor call took: launches per route since the last
+ * reset, process-wide, then the last launch's granule (bytes) and its dynamic
+ * LDS bytes.  One relaxed host increment per launch; meant for tests and
+ * tuning (a settings test that stays on the default route proves nothing). */
+enum {
+    OMPI_AMD_DDT_ROUTE_TILE_PACK_IDENT = 0, /* staged tile, period = one run */
+    OMPI_AMD_DDT_ROUTE_TILE_PACK_MAP,       /* staged tile, byte map */
+    OMPI_AMD_DDT_ROUTE_TILE_UNPACK_IDENT,
+    OMPI_AMD_DDT_ROUTE_TILE_UNPACK_MAP,
+    OMPI_AMD_DDT_ROUTE_VEC16,               /* single element, 16-B chunked walk */
+    OMPI_AMD_DDT_ROUTE_VEC_G,               /* single element, granule < 16 B */
+    OMPI_AMD_DDT_ROUTE_GENERIC32,           /* element search, multiply-high */
+    OMPI_AMD_DDT_ROUTE_GENERIC64,           /* element search, 64-bit indices */
+    OMPI_AMD_DDT_ROUTE_EDGES,               /* byte head / tail launch */
+    OMPI_AMD_DDT_ROUTE_IOV_GENERIC,
+    OMPI_AMD_DDT_ROUTE_IOV_TILE_IDENT,
+    OMPI_AMD_DDT_ROUTE_IOV_TILE_MAP,
+    OMPI_AMD_DDT_LAST_GRANULE,
+    OMPI_AMD_DDT_LAST_LDS,
+    OMPI_AMD_DDT_ROUTE_SLOTS
+};
+/* Copies min(n, OMPI_AMD_DDT_ROUTE_SLOTS) slots into out (NULL: none);
+ * returns OMPI_AMD_DDT_ROUTE_SLOTS. */
+int ompi_amd_ddt_route_counts(int64_t *out, int n);
+void ompi_amd_ddt_route_reset(void);
+
 #ifdef __cplusplus
 }
 #endif

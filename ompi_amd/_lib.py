@@ -112,6 +112,8 @@ PROTOTYPES = [
     ("ompi_amd_ddt_unpack_iov", _C.c_int,
      [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_uint32),
       _C.POINTER(_C.c_size_t), _C.c_void_p]),
+    ("ompi_amd_ddt_route_counts", _C.c_int, [_C.POINTER(_C.c_int64), _C.c_int]),
+    ("ompi_amd_ddt_route_reset", None, []),
     ("ompi_amd_is_device_pointer", _C.c_int, [_C.c_void_p]),
     ("ompi_amd_pointer_range", _C.c_int, [_C.c_void_p, _C.POINTER(_C.c_void_p), _C.POINTER(_C.c_size_t)]),
     ("ompi_amd_memcpy_async", _C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
@@ -389,3 +391,23 @@ def load(path: str = LIB_PATH):
 def check(rc: int, what: str) -> None:
     if rc != SUCCESS:
         raise OmpiAmdError(rc, what)
+
+
+# slots of ompi_amd_ddt_route_counts, in the order of include/ompi_amd_ddt.h
+DDT_ROUTES = ["tile_pack_ident", "tile_pack_map", "tile_unpack_ident", "tile_unpack_map",
+              "vec16", "vec_g", "generic32", "generic64", "edges", "iov_generic",
+              "iov_tile_ident", "iov_tile_map"]
+DDT_ROUTE_SLOTS = DDT_ROUTES + ["last_granule", "last_lds"]
+
+
+def ddt_route_counts() -> dict:
+    """Convertor launches per route since the last reset, plus the last
+    launch's granule and dynamic LDS bytes."""
+    out = (ctypes.c_int64 * len(DDT_ROUTE_SLOTS))()
+    n = load().ompi_amd_ddt_route_counts(out, len(DDT_ROUTE_SLOTS))
+    assert n == len(DDT_ROUTE_SLOTS), n
+    return dict(zip(DDT_ROUTE_SLOTS, [int(v) for v in out]))
+
+
+def ddt_route_reset() -> None:
+    load().ompi_amd_ddt_route_reset()

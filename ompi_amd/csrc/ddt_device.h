@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/ompi_amd_ddt.h"
+#include "ddt_plan.h"
 
 namespace ompi_amd {
 
@@ -15,9 +16,7 @@ namespace ompi_amd {
 // (Granlund-Montgomery round-up method): q = (t + ((n - t) >> s1)) >> s2,
 // t = umulhi(n, m); d = 1 gives m = 0, s1 = s2 = 0.  Exact for every
 // 32-bit n.  Replaces two v_div-style ~40-instruction sequences per granule.
-struct fastdiv {
-    uint32_t m, s1, s2;
-};
+// (struct fastdiv and the host-side make_fdiv: ddt_plan.h)
 
 __device__ __forceinline__ uint32_t fdiv_q(uint32_t n, const fastdiv &f) {
     const uint32_t t = __umulhi(n, f.m);
@@ -80,14 +79,6 @@ __device__ __forceinline__ int64_t typed_offset(const ddt_elem *e, int n, I size
     const I k = r / (I)e[i].blen;
     const I w = r - k * (I)e[i].blen;
     return (int64_t)el * extent + e[i].disp + (int64_t)k * e[i].stride + (int64_t)w;
-}
-
-inline fastdiv make_fdiv(uint32_t d) {  // host side
-    if (d <= 1) return {0u, 0u, 0u};
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;  // ceil(log2 d)
-    const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-    return {(uint32_t)m, 1u, l - 1};
 }
 
 // Fast path: all quantities in G-granule units fit 32 bits.

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -26,6 +27,7 @@
 
 #include "../../include/ompi_amd_ddt.h"
 #include "ddt_device.h"
+#include "ddt_plan.h"
 #include "runtime.h"
 
 namespace ompi_amd {
@@ -612,12 +614,23 @@ static int pow2_gran(uint64_t v) {
     return g;
 }
 
+// Launches per route since the last reset, the last launch's granule and
+// dynamic LDS bytes (ompi_amd_ddt_route_counts): one relaxed host increment
+// per launch, so a test can see which kernel a call took.
+static std::atomic<int64_t> g_routes[OMPI_AMD_DDT_ROUTE_SLOTS];
+static void route_hit(int route, int G, size_t lds) {
+    g_routes[route].fetch_add(1, std::memory_order_relaxed);
+    g_routes[OMPI_AMD_DDT_LAST_GRANULE].store(G, std::memory_order_relaxed);
+    g_routes[OMPI_AMD_DDT_LAST_LDS].store((int64_t)lds, std::memory_order_relaxed);
+}
+
 template <bool UNPACK, typename I>
 static hipError_t launch_g(int G, const ddt_desc &d, const char *src, char *dst,
                            const ddt_window &w, hipStream_t s) {
     int64_t blocks = (w.ngran + kDdtThreads * kDdtUnroll - 1) / (kDdtThreads * kDdtUnroll);
     blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, 1 << 20));
     const dim3 grid((unsigned)blocks), block(kDdtThreads);
+    route_hit(sizeof(I) == 4 ? OMPI_AMD_DDT_ROUTE_GENERIC32 : OMPI_AMD_DDT_ROUTE_GENERIC64, G, 0);
     switch (G) {
     case 16: hipLaunchKernelGGL((ddt_kernel<16, UNPACK, I>), grid, block, 0, s, d, src, dst, w); break;
     case 8: hipLaunchKernelGGL((ddt_kernel<8, UNPACK, I>), grid, block, 0, s, d, src, dst, w); break;
@@ -638,6 +651,7 @@ static hipError_t launch_vec(int G, const ddt_walk &v, const ddt_desc &d, const 
             blocks = std::max<int64_t>(1, std::min<int64_t>(
                 kVecChunkGrid, (w.ngran + kDdtThreads * kVecChunkU - 1) / (kDdtThreads * kVecChunkU)));
         const dim3 grid((unsigned)blocks), block(kDdtThreads);
+        route_hit(G == 16 ? OMPI_AMD_DDT_ROUTE_VEC16 : OMPI_AMD_DDT_ROUTE_VEC_G, G, 0);
         switch (G) {
         case 16: hipLaunchKernelGGL((ddt_vec_kernel<16, UNPACK>), grid, block, 0, s, v, src, dst, w); break;
         case 8: hipLaunchKernelGGL((ddt_vec_kernel<8, UNPACK>), grid, block, 0, s, v, src, dst, w); break;
@@ -646,15 +660,19 @@ static hipError_t launch_vec(int G, const ddt_walk &v, const ddt_desc &d, const 
         default: hipLaunchKernelGGL((ddt_vec_kernel<1, UNPACK>), grid, block, 0, s, v, src, dst, w); break;
         }
     }
-    if (w.head + w.tail > 0)
+    if (w.head + w.tail > 0) {
+        route_hit(OMPI_AMD_DDT_ROUTE_EDGES, G, 0);
         hipLaunchKernelGGL((ddt_vec_edges<UNPACK>), dim3(1), dim3(64), 0, s, d, src, dst, w);
+    }
     return hipGetLastError();
 }
 
 // Staged tile pack / unpack when the layout is periodic, sub-16-B granular (or
 // multi-element) and dense enough.  Returns false when the
 // generic / walker kernels should run instead.
-constexpr int64_t kTileMaxGap = 128;          // bytes of gap the tile reads through
+// The bounds, the settings' accepted ranges and the period arithmetic live in
+// ddt_plan.h (host arithmetic a stand-alone program checks); kTileMaxGap = 128
+// bytes of gap the tile reads through.
 // Run periods (vector-like layouts), unpack: the tile never touches the
 // typed gaps (it reads the packed side and writes runs only), so a gap
 // costs nothing but LDS — vector bl64 (512-B runs, 512-B gaps) unpacks at
@@ -663,108 +681,65 @@ constexpr int64_t kTileMaxGap = 128;          // bytes of gap the tile reads thr
 // gaps multiply its reads (bl64 packed slower staged, 3.74 vs 4.00 TB/s,
 // profiles/r03_ddt_run_maxgap_ab.jsonl).  OMPI_AMD_DDT_RUN_MAXGAP overrides
 // the unpack bound (128 = the round-2 behaviour).
-static int64_t run_max_gap() {
-    static const int64_t v = [] {
-        const char *e = getenv("OMPI_AMD_DDT_RUN_MAXGAP");
-        return e ? std::max<int64_t>(0, atoll(e)) : (int64_t)4096;
-    }();
-    return v;
-}
-constexpr int64_t kTileDataDefault = 16 << 10;  // LDS data bytes per workgroup (tuned)
-constexpr int64_t kTileMinWindow = 256 << 10;   // smaller windows: one generic launch
-
+//
 // Layouts whose granule is already 16 B are staged too (vector bl2 / bl8:
 // +28 / +30 %, profiles/r01_ddt_tile_wide.jsonl); OMPI_AMD_DDT_TILE_WIDE=0
 // restricts the tile to sub-16-B granules and multi-element types.
-static bool tile_wide() {
-    static const bool v = !(getenv("OMPI_AMD_DDT_TILE_WIDE") && atoi(getenv("OMPI_AMD_DDT_TILE_WIDE")) == 0);
-    return v;
-}
-
-static int64_t tile_data_bytes() {
-    static const int64_t v = [] {
-        const char *e = getenv("OMPI_AMD_DDT_TILE_BYTES");
-        const int64_t x = e ? atoll(e) : 0;
-        return (x >= 4096 && x <= (60 << 10)) ? x : kTileDataDefault;
-    }();
-    return v;
-}
-
+//
 // Unpack: the typed-side stores of a layout whose runs are all shorter than
 // 64 B (every store a partial 64-B segment) go non-temporal.  256 MiB
 // packed, one convertor call (profiles/r04_unpack_nt_ab.jsonl): blacs
 // indexed 1.36 -> 1.63 TB/s, struct{int,double} 2.62 -> 3.72, vector bl2
 // (16-B runs) 1.94 -> 3.07; with 64-B runs (bl8) they cost 8 % (5.1 -> 4.7),
 // so longer runs keep plain stores.  OMPI_AMD_DDT_UNPACK_NT=0 / 1 forces.
-static bool unpack_nt(int64_t max_run) {
-    static const int v = [] {
-        const char *e = getenv("OMPI_AMD_DDT_UNPACK_NT");
-        return e ? atoi(e) : -1;
-    }();
-    return v >= 0 ? v != 0 : max_run < 64;
-}
-
+//
 // Unpack: typed bytes one tile spans (its LDS holds only the packed bytes
-// of those periods); OMPI_AMD_DDT_UNPACK_TILE_BYTES, default the pack's —
-// halved for periods of many runs (>= 8 elements): 256 MiB blacs-indexed
-// unpack (13 runs of 4-52 B) 1.62 -> 1.97 TB/s at 8 KiB, while
-// struct{int,double} (2 runs) and vector layouts (1 run) are faster at
-// 16 KiB (profiles/r04_unpack_tile_sweep.jsonl, r04_blacs_sweep_nt.jsonl).
-static int64_t unpack_tile_bytes(size_t runs) {
-    static const int64_t v = [] {
-        const char *e = getenv("OMPI_AMD_DDT_UNPACK_TILE_BYTES");
-        const int64_t x = e ? atoll(e) : 0;
-        return (x >= 1024 && x <= (1 << 20)) ? x : 0;
-    }();
-    if (v) return v;
-    return runs >= 8 ? std::max<int64_t>(4096, tile_data_bytes() / 2) : tile_data_bytes();
-}
-
-static bool tile_off() {
-    static const bool v = getenv("OMPI_AMD_DDT_TILE") && atoi(getenv("OMPI_AMD_DDT_TILE")) == 0;
-    return v;
+// of those periods); OMPI_AMD_DDT_UNPACK_TILE_BYTES (1 KiB .. 128 KiB: the
+// tile and a byte map must fit a workgroup's 160 KiB of LDS, ddt_plan.h),
+// default the pack's — halved for periods of many runs (>= 8 elements):
+// 256 MiB blacs-indexed unpack (13 runs of 4-52 B) 1.62 -> 1.97 TB/s at
+// 8 KiB, while struct{int,double} (2 runs) and vector layouts (1 run) are
+// faster at 16 KiB (profiles/r04_unpack_tile_sweep.jsonl,
+// r04_blacs_sweep_nt.jsonl).
+static const ddt_knobs &knobs() {
+    static const ddt_knobs k = knobs_from(
+        getenv("OMPI_AMD_DDT_TILE"), getenv("OMPI_AMD_DDT_TILE_WIDE"),
+        getenv("OMPI_AMD_DDT_TILE_BYTES"), getenv("OMPI_AMD_DDT_UNPACK_TILE_BYTES"),
+        getenv("OMPI_AMD_DDT_UNPACK_NT"), getenv("OMPI_AMD_DDT_RUN_MAXGAP"));
+    return k;
 }
 
 // The period of the staged tile kernels for this layout (false: not
 // periodic enough, or a gap too wide to read through); *lds = dynamic LDS.
 static bool tile_period(const ompi_amd_ddt_t *ddt, size_t count, int G, bool unpack,
                         ddt_period *out, bool *ident_out, size_t *lds) {
-    if (tile_off()) return false;
-    ddt_period P{};
-    bool ident = false;
     const ddt_elem &x = ddt->host[0];
-    if (ddt->host.size() == 1 && x.count > 1 && (G < 16 || tile_wide()) &&
-        (count == 1 || ddt->extent == x.count * x.stride) && x.stride > 0 &&
-        x.stride - x.blen <= (unpack ? run_max_gap() : kTileMaxGap) &&
-        x.stride <= tile_data_bytes() / 4) {
-        ident = true;  // period = one run
-        P.psize = x.blen;
-        P.pext = x.stride;
-        P.base = x.disp;
-        P.span = x.blen;
-    } else if (ddt->inst_tile && (ddt->host.size() > 1 || G < 16 || tile_wide()) &&
-               ddt->hi - ddt->lo <= tile_data_bytes() / 4) {
-        P.psize = ddt->size;  // period = one instance
-        P.pext = ddt->extent;
-        P.base = ddt->lo;
-        P.span = ddt->hi - ddt->lo;
-        P.map = ddt->dmap;
-        P.map_bytes = (P.psize * 2 + 15) & ~(int64_t)15;
-    } else {
-        return false;
-    }
-    if (P.pext < 0 || P.psize % G != 0) return false;
-    if (unpack && P.psize > P.pext) return false;  // the tile's packed bytes must fit its LDS
-    P.nt = unpack && unpack_nt(ident ? P.psize : ddt->max_blen) ? 1 : 0;
-    const int64_t tb = unpack ? unpack_tile_bytes(ident ? 1 : ddt->host.size()) : tile_data_bytes();
-    P.nper = std::max<int64_t>(1, (tb - P.span) / std::max<int64_t>(P.pext, 1) + 1);
-    // LDS: the map, then the tile's typed span (the unpack stages only the
-    // packed bytes of its periods, but sizing its LDS to those — more
-    // workgroups per CU — measured slower: vector bl64 5.4 -> 4.9 TB/s,
-    // profiles/r04_unpack_tile_sweep.jsonl), + 32 for the 16-B phase
-    *lds = (size_t)P.map_bytes + (size_t)(((P.nper - 1) * P.pext + P.span + 15) & ~(int64_t)15) + 32;
+    ddt_plan_type t;
+    t.nelem = ddt->host.size();
+    t.count0 = x.count;
+    t.blen0 = x.blen;
+    t.stride0 = x.stride;
+    t.disp0 = x.disp;
+    t.size = ddt->size;
+    t.extent = ddt->extent;
+    t.max_blen = ddt->max_blen;
+    t.inst_tile = ddt->inst_tile;
+    t.lo = ddt->lo;
+    t.hi = ddt->hi;
+    ddt_tile_plan p;
+    if (!plan_tile_period(t, count, G, unpack, knobs(), &p)) return false;
+    ddt_period P{};
+    P.psize = p.psize;
+    P.pext = p.pext;
+    P.base = p.base;
+    P.span = p.span;
+    P.nper = p.nper;
+    P.map_bytes = p.map_bytes;
+    P.map = p.ident ? nullptr : ddt->dmap;
+    P.nt = p.nt ? 1 : 0;
+    *lds = p.lds;
     *out = P;
-    *ident_out = ident;
+    *ident_out = p.ident;
     return true;
 }
 
@@ -782,6 +757,10 @@ static bool tile_run(const ompi_amd_ddt_t *ddt, size_t count, int G, char *typed
     const int64_t tiles = (j1 - j0 + P.nper - 1) / P.nper;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, 2048));
     hipError_t e = hipSuccess;
+    if (G == 16 || G == 8 || G == 4 || G == 2 || G == 1)
+        route_hit(UNPACK ? (ident ? OMPI_AMD_DDT_ROUTE_TILE_UNPACK_IDENT : OMPI_AMD_DDT_ROUTE_TILE_UNPACK_MAP)
+                         : (ident ? OMPI_AMD_DDT_ROUTE_TILE_PACK_IDENT : OMPI_AMD_DDT_ROUTE_TILE_PACK_MAP),
+                  G, lds);
 #define TILE(GG)                                                                               \
     case GG:                                                                                   \
         if (UNPACK && ident)                                                                   \
@@ -811,6 +790,7 @@ static bool tile_run(const ompi_amd_ddt_t *ddt, size_t count, int G, char *typed
     // partial periods at the window ends: generic byte mapping
     const ddt_window w{start, start, 0, j0 * P.psize - start, j1 * P.psize, end - j1 * P.psize};
     if (e == hipSuccess && w.head + w.tail > 0) {
+        route_hit(OMPI_AMD_DDT_ROUTE_EDGES, G, 0);
         hipLaunchKernelGGL((ddt_vec_edges<UNPACK>), dim3(1), dim3(kDdtThreads), 0, s, d,
                            UNPACK ? contig : typed, UNPACK ? typed : contig, w);
         e = hipGetLastError();
@@ -978,6 +958,9 @@ static int ddt_iov(const ompi_amd_ddt_t *ddt, size_t count, void *typed, size_t 
         for (int j0 = 0; e == hipSuccess && j0 < jobs; j0 += 65535) {
             const dim3 grid(gx, (unsigned)std::min(65535, jobs - j0));
             const iov_job *tab = t.dev + j0;
+            route_hit(!tiled ? OMPI_AMD_DDT_ROUTE_IOV_GENERIC
+                             : ident ? OMPI_AMD_DDT_ROUTE_IOV_TILE_IDENT : OMPI_AMD_DDT_ROUTE_IOV_TILE_MAP,
+                      G, tiled ? lds : 0);
             if (tiled) {
                 const dim3 tgrid(tgx, grid.y);
 #define IOVT(GG)                                                                                \
@@ -1082,27 +1065,17 @@ int ompi_amd_ddt_create_elems(const ompi_amd_ddt_elem_t *elems, int nelems, int6
     // whose runs leave gaps of at most kTileMaxGap bytes (within an
     // instance and between consecutive instances).
     std::vector<uint16_t> imap;
-    if (d->size <= 8192) {
+    if (d->size <= kInstTileMaxSize) {
         std::vector<std::pair<int64_t, int64_t>> runs;  // [begin, end) typed
         for (const auto &e : d->host)
             for (int64_t k = 0; k < e.count; ++k)
                 runs.emplace_back(e.disp + k * e.stride, e.disp + k * e.stride + e.blen);
-        int64_t lo = runs[0].first, hi = runs[0].second;
-        for (const auto &r : runs) { lo = std::min(lo, r.first); hi = std::max(hi, r.second); }
-        std::vector<std::pair<int64_t, int64_t>> sorted = runs;
-        std::sort(sorted.begin(), sorted.end());
-        int64_t gap = 0, reach = sorted[0].second;
-        for (const auto &r : sorted) {
-            gap = std::max(gap, r.first - reach);
-            reach = std::max(reach, r.second);
-        }
-        gap = std::max(gap, extent - (hi - lo));
-        if (hi - lo < 65536 && gap <= kTileMaxGap && extent > 0) {
+        if (plan_inst_tile(runs, d->size, extent, &d->lo, &d->hi)) {
+            // the byte map in typemap order (the packed stream's), not the
+            // address order the gap rule sorted the runs into
             for (const auto &r : runs)
-                for (int64_t b = r.first; b < r.second; ++b) imap.push_back((uint16_t)(b - lo));
+                for (int64_t b = r.first; b < r.second; ++b) imap.push_back((uint16_t)(b - d->lo));
             d->inst_tile = true;
-            d->lo = lo;
-            d->hi = hi;
         }
     }
     const size_t nb = d->host.size() * sizeof(ddt_elem);
@@ -1165,6 +1138,16 @@ int ompi_amd_ddt_destroy(ompi_amd_ddt_t *ddt) {
     if (ddt->dmap) hip_ignore(hipFree(ddt->dmap));
     delete ddt;
     return OMPI_AMD_SUCCESS;
+}
+
+int ompi_amd_ddt_route_counts(int64_t *out, int n) {
+    for (int i = 0; out && i < n && i < OMPI_AMD_DDT_ROUTE_SLOTS; ++i)
+        out[i] = g_routes[i].load(std::memory_order_relaxed);
+    return OMPI_AMD_DDT_ROUTE_SLOTS;
+}
+
+void ompi_amd_ddt_route_reset(void) {
+    for (auto &c : g_routes) c.store(0, std::memory_order_relaxed);
 }
 
 size_t ompi_amd_ddt_size(const ompi_amd_ddt_t *ddt) { return ddt ? (size_t)ddt->size : 0; }

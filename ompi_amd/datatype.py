@@ -197,6 +197,15 @@ def type_struct(blocklengths, displacements, types) -> Datatype:
     return Datatype("struct", elems, lo or 0, hi, align)
 
 
+def type_create_resized(old: Datatype, lb: int, extent: int) -> Datatype:
+    """MPI_Type_create_resized (ompi_datatype_create_resized.c): the typemap
+    of old with lb and ub = lb + extent set; the extent may be smaller than
+    the typemap's span, zero or negative.  Only the extent reaches the device
+    program: consecutive instances sit `extent` bytes apart."""
+    return Datatype(f"resized({old.name},{lb},{extent})", list(old.elems), lb, lb + extent,
+                    old.align)
+
+
 def _addr(buf) -> int:
     if isinstance(buf, int):
         return buf

@@ -12,12 +12,22 @@ the same bytes (gap bytes untouched)."""
 import numpy as np
 import pytest
 
+from ddt_knob_worker import run_worker
 from ddt_random import rand_type, span_of
+from ompi_amd import _lib
 from ompi_amd import datatype as dd
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+SEEN = {"types": 0, "walk16": 0, "ident": 0}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def route_tally():
+    _lib.ddt_route_reset()
+    SEEN["types"] = SEEN["walk16"] = SEEN["ident"] = 0
+    yield
 
 
 def make_case(seed):
@@ -138,6 +148,7 @@ def test_convertor_random_types(orc, seed):
     bad = np.flatnonzero(got_dst != exp_dst2)
     assert bad.size == 0, f"{what}: iovec unpack differs first at typed byte {bad[:1]}"
     dt.free()
+    SEEN["types"] += 1
 
 
 @pytest.mark.parametrize("seed", range(24))
@@ -179,3 +190,54 @@ def test_walk16_random_vectors(orc, seed):
     bad = np.flatnonzero(fill.cpu().numpy()[:span] != exp_dst)
     assert bad.size == 0, f"{what}: unpack differs first at typed byte {bad[:1]}"
     dt.free()
+    SEEN["walk16"] += 1
+
+
+def test_tile_identity_vector(orc):
+    """The staged tile with one run as the period (no byte map), pack and
+    unpack in one call each: a vector of 16-B runs 16 B apart, 625 KiB packed
+    — the seeds above reach the identity tile only under an iovec train and
+    in the unpack, whose windows their random call lengths leave large enough."""
+    dt = dd.type_vector(40001, 2, 4, dd.predefined("MPI_DOUBLE"))
+    total, span = dt.size, span_of(dt, 1)
+    src = dev_rand(span, 600)
+    exp = orc.pack(dt.runs, dt.extent, 1, src.cpu().numpy()[:span].copy(), 0, total)
+    packed = torch.zeros(total + 64, dtype=torch.uint8, device=DEV)
+    before = _lib.ddt_route_counts()
+    conv = dd.Convertor()
+    conv.prepare_for_send(dt, 1, src)
+    assert conv.pack(packed, total) == (1, total)
+    torch.cuda.synchronize()
+    assert np.array_equal(packed.cpu().numpy()[:total], exp)
+    fill = dev_rand(span, 601)
+    exp_dst = fill.cpu().numpy()[:span].copy()
+    orc.unpack(dt.runs, dt.extent, 1, exp, exp_dst, 0)
+    conv = dd.Convertor()
+    conv.prepare_for_recv(dt, 1, fill)
+    assert conv.unpack(packed, total) == (1, total)
+    torch.cuda.synchronize()
+    assert np.array_equal(fill.cpu().numpy()[:span], exp_dst)
+    after = _lib.ddt_route_counts()
+    assert after["tile_pack_ident"] == before["tile_pack_ident"] + 1
+    assert after["tile_unpack_ident"] == before["tile_unpack_ident"] + 1
+    dt.free()
+    SEEN["ident"] = 1
+
+
+def test_every_kernel_reached():
+    """The claim at the top of this file, from the library's route counters:
+    every route of the dispatcher was taken by some seed above (the identity
+    tile's pack by the directed case).  The 32-bit
+    multiply-high form of the element search is chosen by
+    OMPI_AMD_DDT_FASTDIV=1 at the start of a process, so a fresh child runs
+    two multi-element layouts under it and its counters are added."""
+    if SEEN["types"] != 200 or SEEN["walk16"] != 24 or not SEEN["ident"]:
+        pytest.skip("needs the whole module run in this process")
+    counts = _lib.ddt_route_counts()
+    lines = run_worker({"OMPI_AMD_DDT_FASTDIV": "1"}, cases="indexed9,indexed300",
+                       sizes=str(300 << 10))
+    assert all(ln["ok"] for ln in lines), [ln for ln in lines if not ln["ok"]][:3]
+    for k, v in lines[-1]["routes"].items():
+        counts[k] += v
+    missing = [r for r in _lib.DDT_ROUTES if counts[r] == 0]
+    assert not missing, (missing, counts)
