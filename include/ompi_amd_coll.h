@@ -34,6 +34,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ompi_amd_ddt.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -456,6 +458,60 @@ int ompi_amd_gatherv_init(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes
 int ompi_amd_scatterv_init(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
                            const size_t *sdispls, void *rbuf, size_t rbytes, int root,
                            ompi_amd_plan_t **plan);
+
+/* The seven exchange collectives above over derived datatypes, on the device
+ * (MPI_Alltoall ... MPI_Scatterv with a non-contiguous sendtype / recvtype).
+ * The arguments are the byte forms' with a count per side where those take
+ * one byte count (MPI's sendcount / recvcount: the two sides may describe
+ * the same packed bytes with different types), followed by the two
+ * datatypes.  Counts are ELEMENTS of that side's datatype, displacements are
+ * in units of its EXTENT; a NULL datatype is bytes (size 1, extent 1).  The
+ * sender's store reads through sddt and the receiver's copy-out writes
+ * through rddt, so the data moves as in the byte forms — same three paths,
+ * thresholds, slots, passes and agreement, chosen from PACKED bytes — with
+ * no packed temporary, host copy or extra launch; a slot holds the packed
+ * stream, whichever side passed a datatype.  Bytes a datatype does not own
+ * are never written.  MPI_IN_PLACE as in the byte forms: the one buffer is
+ * described by the receive side (scatter(v): the send side).
+ *   The library keeps the datatype's device program by reference: the
+ * caller keeps sddt / rddt alive until the call's stream work is done, the
+ * request completed or the plan freed.  Datatypes of sides "significant only
+ * at root" may be NULL on the other ranks.
+ *   OMPI_AMD_ERR_BAD_PARAM, before any device work and with no request or
+ * plan coming back: everything the byte forms refuse, in packed bytes
+ * (scount * size(sddt) != rcounts[rank] * size(rddt) in a not-in-place
+ * allgatherv, scount * size(sddt) != rcount * size(rddt) in a not-in-place
+ * alltoall, the root's own pair in gather(v) / scatter(v) likewise), a
+ * datatype with a negative extent, a count * size or displacement * extent
+ * past SIZE_MAX, and a datatype that is no valid device program (a handle
+ * whose program is absent: ompi_amd_ddt_create* and commit never hand one
+ * out, so no public call produces it and no test reaches this return).
+ *   get_param "typed_fused" / "typed_staged" / "typed_landing" count these
+ * calls per path (beside the byte forms' counters, which they move too),
+ * "typed_granule" is the access width (16, 8, 4, 2, 1 bytes) of the last
+ * typed launch and "typed_walk64" the launches that indexed the stream in 64
+ * bits (a pair of 2^32 granules or more; set_param "typed_force64" 1 takes
+ * that walk at any size). */
+#define OMPI_AMD_TYPES_ const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt
+#define OMPI_AMD_TYPED_FORMS_(name, ...)                                                         \
+    int ompi_amd_##name##_typed(ompi_amd_comm_t *comm, __VA_ARGS__, OMPI_AMD_TYPES_, void *stream); \
+    int ompi_amd_i##name##_typed(ompi_amd_comm_t *comm, __VA_ARGS__, OMPI_AMD_TYPES_, void *stream, \
+                                 ompi_amd_request_t **request);                                  \
+    int ompi_amd_##name##_typed_init(ompi_amd_comm_t *comm, __VA_ARGS__, OMPI_AMD_TYPES_,        \
+                                     ompi_amd_plan_t **plan);
+OMPI_AMD_TYPED_FORMS_(alltoall, const void *sbuf, void *rbuf, size_t scount, size_t rcount)
+OMPI_AMD_TYPED_FORMS_(alltoallv, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                      void *rbuf, const size_t *rcounts, const size_t *rdispls)
+OMPI_AMD_TYPED_FORMS_(allgatherv, const void *sbuf, size_t scount, void *rbuf, const size_t *rcounts,
+                      const size_t *rdispls)
+OMPI_AMD_TYPED_FORMS_(gather, const void *sbuf, void *rbuf, size_t scount, size_t rcount, int root)
+OMPI_AMD_TYPED_FORMS_(scatter, const void *sbuf, void *rbuf, size_t scount, size_t rcount, int root)
+OMPI_AMD_TYPED_FORMS_(gatherv, const void *sbuf, size_t scount, void *rbuf, const size_t *rcounts,
+                      const size_t *rdispls, int root)
+OMPI_AMD_TYPED_FORMS_(scatterv, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                      void *rbuf, size_t rcount, int root)
+#undef OMPI_AMD_TYPED_FORMS_
+#undef OMPI_AMD_TYPES_
 
 #ifdef __cplusplus
 }

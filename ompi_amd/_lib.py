@@ -257,6 +257,25 @@ PROTOTYPES = [
     for pre, post, tail in [("", "", [_C.c_void_p]), ("i", "", [_C.c_void_p, _C.POINTER(_C.c_void_p)]),
                             ("", "_init", [_C.POINTER(_C.c_void_p)])]
 ] + [
+    # the exchange collectives over derived datatypes: the operand list, the
+    # send and receive datatype handles, then the three forms' tails
+    (f"ompi_amd_{pre}{name}_typed{post}", _C.c_int, [_C.c_void_p] + ops + [_C.c_void_p, _C.c_void_p] + tail)
+    for name, ops in [
+        ("alltoall", [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_size_t]),
+        ("alltoallv", [_C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+                       _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t)]),
+        ("allgatherv", [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_size_t),
+                        _C.POINTER(_C.c_size_t)]),
+        ("gather", [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_size_t, _C.c_int]),
+        ("scatter", [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_size_t, _C.c_int]),
+        ("gatherv", [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.POINTER(_C.c_size_t),
+                     _C.POINTER(_C.c_size_t), _C.c_int]),
+        ("scatterv", [_C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.c_void_p,
+                      _C.c_size_t, _C.c_int]),
+    ]
+    for pre, post, tail in [("", "", [_C.c_void_p]), ("i", "", [_C.c_void_p, _C.POINTER(_C.c_void_p)]),
+                            ("", "_init", [_C.POINTER(_C.c_void_p)])]
+] + [
     # point-to-point (include/ompi_amd_p2p.h)
     ("ompi_amd_isend", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,

@@ -340,6 +340,38 @@ class Communicator:
         """MPI_Scatterv_init: collective, as gatherv_init."""
         return self._xch("scatterv", 2, self._sv_args(sbuf, scounts, sdispls, rbuf, rbytes, root))
 
+    # -- the exchange collectives over derived datatypes -----------------------
+    # <name>_typed, i<name>_typed and <name>_typed_init for the seven
+    # collectives above (attached below the class, _TYPED_OPERANDS): the
+    # operands of the byte forms with a count per side where those take one
+    # byte count, then sddt, rddt — ompi_amd.datatype.Datatype, committed on
+    # demand; None is bytes.  Counts are elements of that side's datatype,
+    # displacements multiples of its extent.  A request or plan keeps its
+    # datatypes alive.  The blocking form returns nothing that could: it has
+    # synchronized by the time it returns, unless the caller passed a stream
+    # with blocking=False, and then the caller keeps both Datatype objects
+    # alive until that stream's work is done.
+    @staticmethod
+    def _ddt(t):
+        return None if t is None else t.commit()._handle
+
+    def _xch_typed(self, name, form, operands, sddt, rddt, stream=None, blocking=False):
+        args = getattr(self, _TYPED_OPERANDS[name])(*operands) + (self._ddt(sddt), self._ddt(rddt))
+        h = self._xch(name + "_typed", form, args, stream, blocking)
+        if h is not None:
+            h._types = (sddt, rddt)
+        return h
+
+    def _a2a_t(self, sbuf, rbuf, scount, rcount):
+        return (_optr(sbuf), _optr(rbuf), int(scount), int(rcount))
+
+    def _a2av_t(self, sbuf, scounts, sdispls, rbuf, rcounts, rdispls):
+        return (_optr(sbuf), self._osizes(scounts), self._osizes(sdispls), _optr(rbuf),
+                self._osizes(rcounts), self._osizes(rdispls))
+
+    def _rooted_t(self, sbuf, rbuf, scount, rcount, root):
+        return (_optr(sbuf), _optr(rbuf), int(scount), int(rcount), root)
+
     # -- nonblocking forms (coll.h:261-410) -----------------------------------
     def ialltoall(self, sbuf, rbuf, nbytes: int, stream=None) -> "Request":
         h = ctypes.c_void_p()
@@ -474,6 +506,38 @@ class Communicator:
     def __del__(self):
         # destroy is collective; only an explicit free() releases the comm
         pass
+
+
+# The typed forms' operand builders: alltoall_typed(sbuf, rbuf, scount, rcount,
+# sddt, rddt), alltoallv_typed(sbuf, scounts, sdispls, rbuf, rcounts, rdispls,
+# sddt, rddt), allgatherv_typed(sbuf, scount, rbuf, rcounts, rdispls, sddt,
+# rddt), gather_typed / scatter_typed(sbuf, rbuf, scount, rcount, root, sddt,
+# rddt), gatherv_typed(sbuf, scount, rbuf, rcounts, rdispls, root, sddt, rddt),
+# scatterv_typed(sbuf, scounts, sdispls, rbuf, rcount, root, sddt, rddt).
+_TYPED_OPERANDS = {"alltoall": "_a2a_t", "alltoallv": "_a2av_t", "allgatherv": "_agv_args",
+                   "gather": "_rooted_t", "scatter": "_rooted_t", "gatherv": "_gv_args",
+                   "scatterv": "_sv_args"}
+
+
+def _attach_typed(name: str) -> None:
+    def blocking_form(self, *a, stream=None, blocking=False):
+        self._xch_typed(name, 0, a[:-2], a[-2], a[-1], stream, blocking)
+
+    def post_form(self, *a, stream=None) -> "Request":
+        return self._xch_typed(name, 1, a[:-2], a[-2], a[-1], stream)
+
+    def init_form(self, *a) -> "Plan":
+        return self._xch_typed(name, 2, a[:-2], a[-2], a[-1])
+
+    for fn, attr in ((blocking_form, f"{name}_typed"), (post_form, f"i{name}_typed"),
+                     (init_form, f"{name}_typed_init")):
+        fn.__name__ = attr
+        fn.__doc__ = f"MPI_{name.capitalize()} over derived datatypes: (*operands, sddt, rddt)."
+        setattr(Communicator, attr, fn)
+
+
+for _name in _TYPED_OPERANDS:
+    _attach_typed(_name)
 
 
 class Plan:

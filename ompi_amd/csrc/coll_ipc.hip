@@ -390,6 +390,12 @@ struct a2a_call {
     // allgatherv: rdispls[p]), else 0.
     uint8_t ph[kMaxRanks];
     size_t sc[kMaxRanks], sd[kMaxRanks], rc[kMaxRanks], rd[kMaxRanks];
+    // The *_typed forms: the datatype each side walks, by
+    // value (st / rt false: that side is bytes).  sc / rc stay packed bytes;
+    // sd / rd are then the byte offset of the block's typed base
+    // (displacement * extent) and ph[] is 0.
+    bool st, rt;
+    ddt_view sv, rv;
 };
 
 // A nonblocking collective posted but not launched yet.  Device work must
@@ -638,6 +644,13 @@ struct ompi_amd_comm {
     // _staged / _landing / _passes
     int64_t gather_paths[5] = {};
     int64_t gather_passes = 0;
+    // the *_typed forms: calls per path ("typed_fused" / _staged / _landing),
+    // the granule of the last typed launch (the smallest any of its copies
+    // took), launches that ran the 64-bit walk, and param "typed_force64"
+    int64_t typed_paths[5] = {};
+    int64_t typed_granule = 0;
+    int64_t typed_walk64 = 0;
+    int typed_force64 = 0;
     // param "copy_nt": 1 the copy and fold kernels store non-temporally —
     // measured no slower on one GPU at N = 2 / 4 / 8 (scatter, gather and fold
     // kernels 1-5 % faster) — 0 plain stores; -1 (default)
@@ -3561,6 +3574,8 @@ int ompi_amd_comm_set_param(ompi_amd_comm_t *c, const char *key, int64_t v) {
         // a multiple of 256 B (every pass keeps the block's phase mod 16); 0: the default
         if (v < 0 || (v != 0 && v < 256)) return OMPI_AMD_ERR_BAD_PARAM;
         c->alltoall_chunk = (size_t)v & ~(size_t)255;
+    } else if (!strcmp(key, "typed_force64")) {
+        c->typed_force64 = v ? 1 : 0;
     } else if (!strcmp(key, "copy_nt")) {
         c->copy_nt_fixed = v >= 0;
         c->copy_nt = v != 0 ? 1 : 0;
@@ -3645,6 +3660,12 @@ int ompi_amd_comm_get_param(const ompi_amd_comm_t *c, const char *key, int64_t *
     else if (!strcmp(key, "gather_fused")) *v = c->gather_paths[2];
     else if (!strcmp(key, "gather_staged")) *v = c->gather_paths[3];
     else if (!strcmp(key, "gather_landing")) *v = c->gather_paths[4];
+    else if (!strcmp(key, "typed_fused")) *v = c->typed_paths[2];
+    else if (!strcmp(key, "typed_staged")) *v = c->typed_paths[3];
+    else if (!strcmp(key, "typed_landing")) *v = c->typed_paths[4];
+    else if (!strcmp(key, "typed_granule")) *v = c->typed_granule;
+    else if (!strcmp(key, "typed_walk64")) *v = c->typed_walk64;
+    else if (!strcmp(key, "typed_force64")) *v = c->typed_force64;
     else if (!strcmp(key, "copy_nt")) *v = c->copy_nt;
     else if (!strcmp(key, "copy_nt_fixed")) *v = c->copy_nt_fixed;
     else if (!strcmp(key, "unsafe_exports")) *v = c->unsafe_exports;
@@ -4830,6 +4851,134 @@ static size_t a2a_local_max(const ompi_amd_comm_t *c, const a2a_call &k) {
     return m;
 }
 
+// ---- typed ends ----
+static bool a2a_typed(const a2a_call &k) { return k.st || k.rt; }
+
+static typed_end end_of(bool on, const ddt_view &v) {
+    typed_end e{};
+    if (!on) return e;
+    e.d = v.d;
+    e.gran = v.gran;
+    for (int lg = 0; lg < 5; ++lg) {
+        const int64_t sg = v.d.size >> lg;
+        if ((v.d.size & ((1 << lg) - 1)) == 0 && sg < (1ll << 32)) e.sdiv[lg] = make_fdiv((uint32_t)sg);
+    }
+    return e;
+}
+
+// What the copies of one typed launch pick (coll_typed.h's rule, which the
+// kernel evaluates again per copy): the smallest granule, any 64-bit walk.
+struct typed_note {
+    int g = 16;
+    bool w64 = false, any = false;
+};
+static void note_copy(const ompi_amd_comm_t *c, typed_note *tn, const ddt_view &v, const void *typed,
+                      const void *contig, size_t pair) {
+    if (!pair) return;
+    const int G = typed_granule(v.gran, (uint64_t)(uintptr_t)typed, (uint64_t)(uintptr_t)contig);
+    tn->g = std::min(tn->g, G);
+    tn->w64 = tn->w64 || typed_walk64(pair, G, c->typed_force64 != 0);
+    tn->any = true;
+}
+static void note_launch(ompi_amd_comm_t *c, const typed_note &tn) {
+    if (!tn.any) return;
+    c->typed_granule = tn.g;
+    if (tn.w64) ++c->typed_walk64;
+}
+
+static int launch_typed_copy(ompi_amd_comm_t *c, const a2a_call &k, tcp_jobs &jobs, hipStream_t s) {
+    if (jobs.n == 0) return OMPI_AMD_SUCCESS;
+    note_stream(c, s);
+    jobs.se = end_of(k.st, k.sv);
+    jobs.re = end_of(k.rt, k.rv);
+    jobs.force64 = c->typed_force64;
+    typed_note tn;
+    int64_t most = 0;
+    for (int i = 0; i < jobs.n; ++i) {
+        const tcp_job &j = jobs.j[i];
+        most = std::max(most, j.hi - j.lo);
+        if (j.typed == TCP_SRC_TYPED) note_copy(c, &tn, k.sv, j.src, j.dst + j.lo, (size_t)j.pair);
+        else if (j.typed == TCP_DST_TYPED) note_copy(c, &tn, k.rv, j.dst, j.src + j.lo, (size_t)j.pair);
+    }
+    int64_t blocks = (most / 16 + kXferThreads * 4 - 1) / (kXferThreads * 4);
+    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, std::max(1, c->max_blocks / jobs.n)));
+    if (c->copy_nt)
+        hipLaunchKernelGGL(typed_copy_kernel<true>, dim3((unsigned)blocks, (unsigned)jobs.n),
+                           dim3(kXferThreads), 0, s, jobs);
+    else
+        hipLaunchKernelGGL(typed_copy_kernel<false>, dim3((unsigned)blocks, (unsigned)jobs.n),
+                           dim3(kXferThreads), 0, s, jobs);
+    TRY(record_hip(hipGetLastError(), "typed copy launch"));
+    note_launch(c, tn);
+    return OMPI_AMD_SUCCESS;
+}
+
+// alltoall_exchange below with a datatype on either end.  A slot holds stream
+// bytes [off, off + chunk) of its pair from its first byte on (phase 0), so a
+// contiguous end's stream byte 0 is `off` bytes before the slot.  My own
+// block goes directly while at most one side is typed (one walk, the other
+// end contiguous) and through my own slot when both are.
+static int alltoall_exchange_typed(ompi_amd_comm_t *c, const a2a_call &k, size_t off, size_t chunk,
+                                   char *mine, const ptr_set &peers, size_t slot, int slots,
+                                   bool trailing, hipStream_t s) {
+    const int n = c->size, me = c->rank;
+    const bool both = k.st && k.rt;
+    auto at = [&](int p) { return (size_t)(slots == 1 ? 0 : p) * slot; };
+    auto piece = [&](size_t cnt, int64_t *lo, int64_t *hi) {
+        *lo = (int64_t)std::min(cnt, off);
+        *hi = (int64_t)std::min(cnt, off + chunk);
+    };
+    int64_t lo, hi;
+    tcp_jobs tj{};
+    for (int i = 0; i < n; ++i) {  // my own block, then peers rank+1, rank+2, ...
+        const int q = (me + i) % n;
+        piece(k.sc[q], &lo, &hi);
+        if (hi == lo || (i == 0 && k.inplace)) continue;
+        const bool direct = i == 0 && !both;
+        char *d = direct ? k.rbuf + k.rd[me]
+                         : (i == 0 ? mine : const_cast<char *>(peers.p[q])) + at(me) - off;
+        const int typed = k.st ? TCP_SRC_TYPED : (direct && k.rt ? TCP_DST_TYPED : TCP_BYTES);
+        tj.j[tj.n++] = {k.sbuf + k.sd[q], d, lo, hi, (int64_t)k.sc[q], typed};
+    }
+    TRY(launch_typed_copy(c, k, tj, s));
+    TRY(launch_barrier(c, s));
+    tj = tcp_jobs{};
+    for (int p = 0; p < n; ++p) {
+        piece(k.rc[p], &lo, &hi);
+        if (hi == lo || (p == me && !(both && !k.inplace))) continue;
+        tj.j[tj.n++] = {mine + at(p) - off, k.rbuf + k.rd[p], lo, hi, (int64_t)k.rc[p],
+                        k.rt ? TCP_DST_TYPED : TCP_BYTES};
+    }
+    TRY(launch_typed_copy(c, k, tj, s));
+    return trailing ? launch_barrier(c, s) : OMPI_AMD_SUCCESS;
+}
+
+// One rank: the block moves by one typed copy, or — both sides typed —
+// through a scratch half in passes of what it holds (pack, then unpack; the
+// stream orders the passes).
+static int alltoall_local_typed(ompi_amd_comm_t *c, const a2a_call &k, hipStream_t s) {
+    if (k.inplace || !k.sc[0]) return OMPI_AMD_SUCCESS;
+    const int64_t total = (int64_t)k.sc[0];
+    tcp_jobs tj{};
+    if (!(k.st && k.rt)) {
+        tj.j[tj.n++] = {k.sbuf + k.sd[0], k.rbuf + k.rd[0], 0, total, total,
+                        k.st ? TCP_SRC_TYPED : TCP_DST_TYPED};
+        return launch_typed_copy(c, k, tj, s);
+    }
+    const stage_half sh = next_half(c);
+    const int64_t chunk = (int64_t)(c->scratch_bytes & ~(size_t)255);
+    for (int64_t off = 0; off < total; off += chunk) {
+        const int64_t hi = std::min(total, off + chunk);
+        tj = tcp_jobs{};
+        tj.j[tj.n++] = {k.sbuf + k.sd[0], sh.mine - off, off, hi, total, TCP_SRC_TYPED};
+        TRY(launch_typed_copy(c, k, tj, s));
+        tj = tcp_jobs{};
+        tj.j[tj.n++] = {sh.mine - off, k.rbuf + k.rd[0], off, hi, total, TCP_DST_TYPED};
+        TRY(launch_typed_copy(c, k, tj, s));
+    }
+    return OMPI_AMD_SUCCESS;
+}
+
 static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipStream_t s) {
     note_stream(c, s);
     const int n = c->size, me = c->rank;
@@ -4864,7 +5013,30 @@ static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipSt
         a.mark = c->mark_word;
         a.mark_v = mark_reserve();
     }
-    if (k.coll == XCH_ALLGATHERV) {  // one block to every peer: load once, store N times
+    if (a2a_typed(k)) {
+        // typed ends: the allgatherv too (its load-once multicast stays a
+        // bytes-only optimisation)
+        typed_a2a_args ta{a, end_of(k.st, k.sv), end_of(k.rt, k.rv), c->typed_force64};
+        const bool both = k.st && k.rt;
+        typed_note tn;
+        for (int q = 0; q < n; ++q) {
+            if (q == me && k.inplace) continue;
+            const bool direct = q == me && !both;
+            const char *d = direct ? k.rbuf + k.rd[me]
+                                   : (q == me ? sh.mine : sh.peers.p[q]) + (size_t)me * (size_t)a.slot;
+            if (k.st) note_copy(c, &tn, k.sv, k.sbuf + k.sd[q], d, k.sc[q]);
+            else if (direct && k.rt) note_copy(c, &tn, k.rv, d, k.sbuf + k.sd[q], k.sc[q]);
+        }
+        for (int p = 0; p < n && k.rt; ++p) {
+            if (p == me && !(both && !k.inplace)) continue;
+            note_copy(c, &tn, k.rv, k.rbuf + k.rd[p], sh.mine + (size_t)p * (size_t)a.slot, k.rc[p]);
+        }
+        if (c->copy_nt)
+            hipLaunchKernelGGL(fused_alltoall_typed_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, ta);
+        else
+            hipLaunchKernelGGL(fused_alltoall_typed_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, ta);
+        note_launch(c, tn);
+    } else if (k.coll == XCH_ALLGATHERV) {  // one block to every peer: load once, store N times
         if (c->copy_nt)
             hipLaunchKernelGGL(fused_allgatherv_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, a);
         else
@@ -4885,6 +5057,7 @@ static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipSt
 static int alltoall_exchange(ompi_amd_comm_t *c, const a2a_call &k, size_t off, size_t chunk,
                              char *mine, const ptr_set &peers, size_t slot, int slots, bool trailing,
                              hipStream_t s) {
+    if (a2a_typed(k)) return alltoall_exchange_typed(c, k, off, chunk, mine, peers, slot, slots, trailing, s);
     const int n = c->size, me = c->rank;
     auto at = [&](int p) { return (size_t)(slots == 1 ? 0 : p) * slot + a2a_phase(k, p); };
     auto piece = [&](size_t cnt, size_t *lo, size_t *len) {
@@ -4944,9 +5117,11 @@ static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const p
                         size_t chunk, bool may_grow, hipStream_t s) {
     const int path = a2a_path(c, pp, M);
     ++(k.coll == XCH_ALLTOALL ? c->alltoall_paths : c->gather_paths)[path];
+    if (a2a_typed(k)) ++c->typed_paths[path];
     if (path == A2A_NONE) return OMPI_AMD_SUCCESS;
     TRY(set_dev(c));
     if (path == A2A_LOCAL) {
+        if (a2a_typed(k)) return alltoall_local_typed(c, k, s);
         cp_jobs cj{};
         if (!k.inplace && k.sc[0]) cj.j[cj.n++] = {k.sbuf + k.sd[0], k.rbuf + k.rd[0], (int64_t)k.sc[0]};
         return launch_copy(c, cj, s);
@@ -5119,12 +5294,75 @@ static int xch_enter(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree
     return OMPI_AMD_SUCCESS;
 }
 
+// The *_typed forms: each side's datatype as the entry
+// points take it.  NULL is bytes: size 1, extent 1, no walk.
+struct typed_pair {
+    bool st = false, rt = false;
+    ddt_view sv{}, rv{};
+    size_t ssz = 1, rsz = 1;     // packed bytes per element
+    int64_t sext = 1, rext = 1;  // bytes from one element to the next
+};
+static int typed_pair_of(const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt, typed_pair *t) {
+    *t = typed_pair{};
+    if (sddt) {
+        if (!ddt_view_of(sddt, &t->sv)) return OMPI_AMD_ERR_BAD_PARAM;
+        t->st = true;
+        t->ssz = (size_t)t->sv.d.size;
+        t->sext = t->sv.d.extent;
+        if (t->sext < 0) return OMPI_AMD_ERR_BAD_PARAM;  // displacement * extent is a size_t
+    }
+    if (rddt) {
+        if (!ddt_view_of(rddt, &t->rv)) return OMPI_AMD_ERR_BAD_PARAM;
+        t->rt = true;
+        t->rsz = (size_t)t->rv.d.size;
+        t->rext = t->rv.d.extent;
+        if (t->rext < 0) return OMPI_AMD_ERR_BAD_PARAM;
+    }
+    return OMPI_AMD_SUCCESS;
+}
+// elements -> packed bytes, displacements -> byte offsets of the typed base
+// (a null array stays null: "significant only at root")
+// A product past SIZE_MAX sets *bad, which the caller turns into BAD_PARAM
+// before anything is launched (the byte forms have no such products).
+static size_t mul_or_bad(size_t a, size_t b, bool *bad) {
+    size_t r = 0;
+    if (__builtin_mul_overflow(a, b, &r)) *bad = true;
+    return r;
+}
+static const size_t *scaled(const size_t *in, int n, size_t by, size_t *out, bool *bad) {
+    if (!in) return nullptr;
+    for (int p = 0; p < n; ++p) out[p] = mul_or_bad(in[p], by, bad);
+    return out;
+}
+// A call that came through a *_typed entry point: the views, and phase 0 in
+// every slot whether or not THIS rank passed a datatype (its peer may have).
+// In place there is one buffer and one datatype: the significant side's.
+static void a2a_types(a2a_call *k, const typed_pair *t) {
+    if (!t) return;
+    k->st = t->st;
+    k->rt = t->rt;
+    k->sv = t->sv;
+    k->rv = t->rv;
+    if (k->inplace) {
+        if (k->coll == XCH_SCATTER) {
+            k->rt = k->st;
+            k->rv = k->sv;
+        } else {
+            k->st = k->rt;
+            k->sv = k->rv;
+        }
+    }
+    memset(k->ph, 0, sizeof(k->ph));
+}
+
 static int allgatherv_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf,
-                            const size_t *rc, const size_t *rd, const xch_form &f) {
+                            const size_t *rc, const size_t *rd, const xch_form &f,
+                            const typed_pair *t = nullptr) {
     TRY(xch_form_ok(c, f));
     if (!rc || !rd) return OMPI_AMD_ERR_BAD_PARAM;
     a2a_call k;
     a2a_allgatherv(c, sbuf, sbytes, rbuf, rc, rd, &k);
+    a2a_types(&k, t);
     size_t M = 0;
     for (int p = 0; p < c->size; ++p) M = std::max(M, rc[p]);
     if (M > 0 && !rbuf) return OMPI_AMD_ERR_BAD_PARAM;
@@ -5134,13 +5372,15 @@ static int allgatherv_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes,
 
 // B != 0 or rc == null at the root: the uniform gather (see a2a_gather)
 static int gather_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, void *rbuf, size_t B,
-                        const size_t *rc, const size_t *rd, int root, bool vec, const xch_form &f) {
+                        const size_t *rc, const size_t *rd, int root, bool vec, const xch_form &f,
+                        const typed_pair *t = nullptr) {
     TRY(xch_form_ok(c, f));
     if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
     const bool at_root = c->rank == root;
     if (at_root && vec && (!rc || !rd)) return OMPI_AMD_ERR_BAD_PARAM;
     a2a_call k;
-    a2a_gather(c, sbuf, sbytes, rbuf, B, vec ? rc : nullptr, vec ? rd : nullptr, root, &k);
+    a2a_gather(c, sbuf, sbytes, rbuf, B, rc, rd, root, &k);
+    a2a_types(&k, t);
     if (at_root) {
         size_t most = 0;
         for (int p = 0; p < c->size; ++p) most = std::max(most, k.rc[p]);
@@ -5153,13 +5393,14 @@ static int gather_enter(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, voi
 
 static int scatter_enter(ompi_amd_comm_t *c, const void *sbuf, size_t B, const size_t *sc,
                          const size_t *sd, void *rbuf, size_t rbytes, int root, bool vec,
-                         const xch_form &f) {
+                         const xch_form &f, const typed_pair *t = nullptr) {
     TRY(xch_form_ok(c, f));
     if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
     const bool at_root = c->rank == root;
     if (at_root && vec && (!sc || !sd)) return OMPI_AMD_ERR_BAD_PARAM;
     a2a_call k;
-    a2a_scatter(c, sbuf, B, vec ? sc : nullptr, vec ? sd : nullptr, rbuf, rbytes, root, &k);
+    a2a_scatter(c, sbuf, B, sc, sd, rbuf, rbytes, root, &k);
+    a2a_types(&k, t);
     if (at_root) {
         size_t most = 0;
         for (int p = 0; p < c->size; ++p) most = std::max(most, k.sc[p]);
@@ -5204,6 +5445,158 @@ XCH_FORMS(scatterv,
           XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
                 void *rbuf, size_t rbytes, int root),
           scatter_enter(c, sbuf, 0, scounts, sdispls, rbuf, rbytes, root, true, f))
+
+// ---- the *_typed forms: counts in elements, displacements in extents ----
+static int alltoall_typed_enter(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t scount,
+                                size_t rcount, const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt,
+                                const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    typed_pair t;
+    TRY(typed_pair_of(sddt, rddt, &t));
+    const bool inplace = in_place(sbuf, rbuf);
+    bool bad = false;
+    const size_t B = mul_or_bad(rcount, t.rsz, &bad);
+    if (!inplace && mul_or_bad(scount, t.ssz, &bad) != B) return OMPI_AMD_ERR_BAD_PARAM;
+    if ((!rbuf || !sbuf) && B > 0) return OMPI_AMD_ERR_BAD_PARAM;
+    size_t sc[kMaxRanks], sd[kMaxRanks], rc[kMaxRanks], rd[kMaxRanks];
+    for (int p = 0; p < c->size; ++p) {
+        sc[p] = rc[p] = B;
+        sd[p] = inplace ? 0 : mul_or_bad((size_t)p, mul_or_bad(scount, (size_t)t.sext, &bad), &bad);
+        rd[p] = mul_or_bad((size_t)p, mul_or_bad(rcount, (size_t)t.rext, &bad), &bad);
+    }
+    if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_call k;
+    a2a_vector(c, sbuf, sc, sd, rbuf, rc, rd, &k);
+    a2a_types(&k, &t);
+    return xch_enter(c, k, B, false, f);
+}
+
+static int alltoallv_typed_enter(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts,
+                                 const size_t *sdispls, void *rbuf, const size_t *rcounts,
+                                 const size_t *rdispls, const ompi_amd_ddt_t *sddt,
+                                 const ompi_amd_ddt_t *rddt, const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    TRY(a2av_args_ok(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls));
+    typed_pair t;
+    TRY(typed_pair_of(sddt, rddt, &t));
+    size_t sc[kMaxRanks], sd[kMaxRanks], rc[kMaxRanks], rd[kMaxRanks];
+    a2a_call k;
+    bool bad = false;
+    const size_t *psc = scaled(scounts, c->size, t.ssz, sc, &bad);
+    const size_t *psd = scaled(sdispls, c->size, (size_t)t.sext, sd, &bad);
+    const size_t *prc = scaled(rcounts, c->size, t.rsz, rc, &bad);
+    const size_t *prd = scaled(rdispls, c->size, (size_t)t.rext, rd, &bad);
+    if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+    a2a_vector(c, sbuf, psc, psd, rbuf, prc, prd, &k);
+    a2a_types(&k, &t);
+    return xch_enter(c, k, a2a_local_max(c, k), true, f);
+}
+
+static int allgatherv_typed_enter(ompi_amd_comm_t *c, const void *sbuf, size_t scount, void *rbuf,
+                                  const size_t *rcounts, const size_t *rdispls,
+                                  const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt,
+                                  const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    typed_pair t;
+    TRY(typed_pair_of(sddt, rddt, &t));
+    size_t rc[kMaxRanks], rd[kMaxRanks];
+    bool bad = false;
+    const size_t sbytes = mul_or_bad(scount, t.ssz, &bad);
+    const size_t *prc = scaled(rcounts, c->size, t.rsz, rc, &bad);
+    const size_t *prd = scaled(rdispls, c->size, (size_t)t.rext, rd, &bad);
+    if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+    return allgatherv_enter(c, sbuf, sbytes, rbuf, prc, prd, f, &t);
+}
+
+// vec false: the uniform gather / scatter.  Its blocks sit count * extent
+// apart at the root, which is not count * size, so the root passes the
+// engine a row of counts and offsets; the largest pair is still known
+// locally (no agreement), from whichever count is significant on this rank.
+static int gather_typed_enter(ompi_amd_comm_t *c, const void *sbuf, size_t scount, void *rbuf,
+                              size_t rcount, const size_t *rcounts, const size_t *rdispls, int root,
+                              bool vec, const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt,
+                              const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
+    typed_pair t;
+    TRY(typed_pair_of(sddt, rddt, &t));
+    const bool at_root = c->rank == root;
+    size_t rc[kMaxRanks], rd[kMaxRanks];
+    bool bad = false;
+    const size_t sbytes = mul_or_bad(scount, t.ssz, &bad);
+    if (vec) {
+        const size_t *prc = scaled(rcounts, c->size, t.rsz, rc, &bad);
+        const size_t *prd = scaled(rdispls, c->size, (size_t)t.rext, rd, &bad);
+        if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+        return gather_enter(c, sbuf, sbytes, rbuf, 0, prc, prd, root, true, f, &t);
+    }
+    const size_t rbytes = at_root ? mul_or_bad(rcount, t.rsz, &bad) : 0;
+    for (int p = 0; at_root && p < c->size; ++p) {
+        rc[p] = rbytes;
+        rd[p] = mul_or_bad((size_t)p, mul_or_bad(rcount, (size_t)t.rext, &bad), &bad);
+    }
+    if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+    return gather_enter(c, sbuf, sbytes, rbuf, at_root ? rbytes : sbytes, at_root ? rc : nullptr,
+                        at_root ? rd : nullptr, root, false, f, &t);
+}
+
+static int scatter_typed_enter(ompi_amd_comm_t *c, const void *sbuf, size_t scount,
+                               const size_t *scounts, const size_t *sdispls, void *rbuf, size_t rcount,
+                               int root, bool vec, const ompi_amd_ddt_t *sddt,
+                               const ompi_amd_ddt_t *rddt, const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    if (root < 0 || root >= c->size) return OMPI_AMD_ERR_BAD_PARAM;
+    typed_pair t;
+    TRY(typed_pair_of(sddt, rddt, &t));
+    const bool at_root = c->rank == root;
+    size_t sc[kMaxRanks], sd[kMaxRanks];
+    bool bad = false;
+    const size_t rbytes = mul_or_bad(rcount, t.rsz, &bad);
+    if (vec) {
+        const size_t *psc = scaled(scounts, c->size, t.ssz, sc, &bad);
+        const size_t *psd = scaled(sdispls, c->size, (size_t)t.sext, sd, &bad);
+        if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+        return scatter_enter(c, sbuf, 0, psc, psd, rbuf, rbytes, root, true, f, &t);
+    }
+    const size_t sbytes = at_root ? mul_or_bad(scount, t.ssz, &bad) : 0;
+    for (int p = 0; at_root && p < c->size; ++p) {
+        sc[p] = sbytes;
+        sd[p] = mul_or_bad((size_t)p, mul_or_bad(scount, (size_t)t.sext, &bad), &bad);
+    }
+    if (bad) return OMPI_AMD_ERR_BAD_PARAM;
+    return scatter_enter(c, sbuf, at_root ? sbytes : rbytes, at_root ? sc : nullptr,
+                         at_root ? sd : nullptr, rbuf, rbytes, root, false, f, &t);
+}
+
+#define XCH_T const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt
+XCH_FORMS(alltoall_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t scount, size_t rcount, XCH_T),
+          alltoall_typed_enter(c, sbuf, rbuf, scount, rcount, sddt, rddt, f))
+XCH_FORMS(alltoallv_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                void *rbuf, const size_t *rcounts, const size_t *rdispls, XCH_T),
+          alltoallv_typed_enter(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls, sddt, rddt, f))
+XCH_FORMS(allgatherv_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, size_t scount, void *rbuf, const size_t *rcounts,
+                const size_t *rdispls, XCH_T),
+          allgatherv_typed_enter(c, sbuf, scount, rbuf, rcounts, rdispls, sddt, rddt, f))
+XCH_FORMS(gather_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t scount, size_t rcount, int root,
+                XCH_T),
+          gather_typed_enter(c, sbuf, scount, rbuf, rcount, nullptr, nullptr, root, false, sddt, rddt, f))
+XCH_FORMS(scatter_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, void *rbuf, size_t scount, size_t rcount, int root,
+                XCH_T),
+          scatter_typed_enter(c, sbuf, scount, nullptr, nullptr, rbuf, rcount, root, false, sddt, rddt, f))
+XCH_FORMS(gatherv_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, size_t scount, void *rbuf, const size_t *rcounts,
+                const size_t *rdispls, int root, XCH_T),
+          gather_typed_enter(c, sbuf, scount, rbuf, 0, rcounts, rdispls, root, true, sddt, rddt, f))
+XCH_FORMS(scatterv_typed,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                void *rbuf, size_t rcount, int root, XCH_T),
+          scatter_typed_enter(c, sbuf, 0, scounts, sdispls, rbuf, rcount, root, true, sddt, rddt, f))
+#undef XCH_T
 #undef XCH_FORMS
 #undef XCH_P
 

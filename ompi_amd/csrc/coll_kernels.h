@@ -11,6 +11,8 @@
 #include <cstdint>
 
 #include "../../include/ompi_amd_coll.h"
+#include "coll_typed.h"
+#include "ddt_device.h"
 #include "op_device.h"
 
 namespace ompi_amd {
@@ -881,6 +883,201 @@ __global__ __launch_bounds__(kXferThreads) void fused_allgatherv_kernel(a2a_args
         if (p == a.rank) continue;
         a2a_slice(a.rcount[p], g, G, &lo, &hi);
         pipe_copy(a.mine + (int64_t)p * a.slot + a.rphase[p], a.rbuf + a.rdispl[p], lo, hi, false);
+    }
+    if (a.mark) {  // the host-observed completion, by the last workgroup
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (t == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            if (__hip_atomic_fetch_add(a.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
+                (uint32_t)G - 1) {
+                __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.mark, a.mark_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- typed exchange
+// One end of an exchange copy that walks a derived datatype (ddt_device.h):
+// the program, its granule, and size / G as a multiply-high divisor for
+// every G the walk may pick.  d.elems == nullptr: the end is plain bytes.
+struct typed_end {
+    ddt_desc d;
+    fastdiv sdiv[5];  // size / G for G = 1, 2, 4, 8, 16 (where G divides the size and it fits 32 bits)
+    int gran;
+};
+
+// ng G-byte granules from stream byte lo on: `typed` is the typed base of the
+// block, `contig` the address of stream byte lo.  kDdtUnroll typed addresses
+// first, then as many independent loads in flight, then the stores
+// (ddt_kernels.hip's ddt_body, by one workgroup).
+template <int G, bool UNPACK>
+__device__ __forceinline__ void typed_walk(const typed_end &e, char *typed, char *contig, int64_t lo,
+                                           int64_t ng, bool nt, bool w64) {
+    using T = typename granule<G>::t;
+    constexpr int U = kDdtUnroll, S = kXferThreads;
+    constexpr int LG = G == 16 ? 4 : G == 8 ? 3 : G == 4 ? 2 : G == 2 ? 1 : 0;
+    const ddt_elem *el = e.d.elems;
+    const int n = e.d.nelem;
+    const uint32_t size_g = (uint32_t)(e.d.size >> LG);
+    const fastdiv sdiv = e.sdiv[LG];
+    const T *cs = reinterpret_cast<const T *>(contig);
+    T *cd = reinterpret_cast<T *>(contig);
+    for (int64_t j0 = threadIdx.x; j0 < ng; j0 += (int64_t)S * U) {
+        int64_t toff[U];
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t j = j0 + u * S;
+            if (j < ng)
+                toff[u] = w64 ? typed_offset<int64_t>(el, n, e.d.size, e.d.extent, lo + j * G)
+                              : typed_offset_fast<G>(el, n, size_g, sdiv, e.d.extent,
+                                                     (uint32_t)((lo >> LG) + j));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t j = j0 + u * S;
+            if (j < ng)
+                v[u] = UNPACK ? __builtin_nontemporal_load(cs + j)
+                              : *reinterpret_cast<const T *>(typed + toff[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t j = j0 + u * S;
+            if (j < ng) {
+                if (UNPACK) *reinterpret_cast<T *>(typed + toff[u]) = v[u];
+                else if (nt) __builtin_nontemporal_store(v[u], cd + j);
+                else cd[j] = v[u];
+            }
+        }
+    }
+}
+
+// Packed-stream bytes [lo, hi) of a pair of `pair` packed bytes, by one
+// workgroup: between the typed layout of e based at `typed` and contiguous
+// memory whose stream byte 0 is at `contig` (UNPACK: contiguous -> typed).
+// nt: the contiguous end is a peer's memory, store non-temporally.  The
+// granule and the walk are coll_typed.h's rule; lo enters the granule beside
+// the contiguous address, so a range cut anywhere is still moved by aligned
+// accesses (the engine cuts at multiples of 16).  Bytes past the last whole
+// granule — none when [lo, hi) ends on an element or a 16-B cut — go bytewise.
+template <bool UNPACK>
+__device__ __forceinline__ void typed_pipe_copy(const typed_end &e, char *typed, char *contig, int64_t lo,
+                                                int64_t hi, int64_t pair, bool nt, bool force64) {
+    if (hi <= lo) return;
+    char *c = contig + lo;
+    const int G = typed_granule(e.gran, (uint64_t)(uintptr_t)typed, (uint64_t)(uintptr_t)c | (uint64_t)lo);
+    const int64_t ng = (hi - lo) / G;
+    const bool w64 = typed_walk64((uint64_t)pair, G, force64);
+    switch (G) {
+    case 16: typed_walk<16, UNPACK>(e, typed, c, lo, ng, nt, w64); break;
+    case 8: typed_walk<8, UNPACK>(e, typed, c, lo, ng, nt, w64); break;
+    case 4: typed_walk<4, UNPACK>(e, typed, c, lo, ng, nt, w64); break;
+    case 2: typed_walk<2, UNPACK>(e, typed, c, lo, ng, nt, w64); break;
+    default: typed_walk<1, UNPACK>(e, typed, c, lo, ng, nt, w64); break;
+    }
+    for (int64_t p = lo + ng * G + threadIdx.x; p < hi; p += kXferThreads) {
+        const int64_t t = typed_offset<int64_t>(e.d.elems, e.d.nelem, e.d.size, e.d.extent, p);
+        if (UNPACK) typed[t] = contig[p];
+        else contig[p] = typed[t];
+    }
+}
+
+// copy_kernel's job table with an optional datatype on one end of a job:
+// job blockIdx.y moves stream bytes [lo, hi) of its pair, workgroup
+// blockIdx.x the a2a_slice of them.  A typed end is the block's typed base,
+// a contiguous end the address of stream byte 0.  (Both ends typed never
+// meet in one job: such a block goes through a slot, §3.5.)
+enum { TCP_BYTES = 0, TCP_SRC_TYPED = 1, TCP_DST_TYPED = 2 };
+struct tcp_job {
+    const char *src;
+    char *dst;
+    int64_t lo, hi, pair;
+    int typed;  // TCP_*
+};
+struct tcp_jobs {
+    tcp_job j[kMaxRanks];
+    int n;
+    int force64;
+    typed_end se, re;  // the send datatype (TCP_SRC_TYPED), the receive datatype (TCP_DST_TYPED)
+};
+
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void typed_copy_kernel(tcp_jobs jobs) {
+    acquire_once();
+    const tcp_job jb = jobs.j[blockIdx.y];
+    int64_t lo, hi;
+    a2a_slice(jb.hi - jb.lo, (int)blockIdx.x, (int)gridDim.x, &lo, &hi);
+    lo += jb.lo;
+    hi += jb.lo;
+    if (jb.typed == TCP_SRC_TYPED)
+        typed_pipe_copy<false>(jobs.se, const_cast<char *>(jb.src), jb.dst, lo, hi, jb.pair, NT,
+                               jobs.force64 != 0);
+    else if (jb.typed == TCP_DST_TYPED)
+        typed_pipe_copy<true>(jobs.re, jb.dst, const_cast<char *>(jb.src), lo, hi, jb.pair, false,
+                              jobs.force64 != 0);
+    else
+        pipe_copy(jb.src, jb.dst, lo, hi, NT);
+    xfer_epilogue();
+}
+
+// fused_alltoall_kernel with typed ends: workgroup g moves packed bytes
+// a2a_slice(count, g, G) of every block, reading the send layout on the way
+// out and writing the receive layout on the way in; a slot holds the packed
+// stream at phase 0.  My own block goes directly when at most one side is
+// typed, and through my own slot [me] when both are.  The protocol — drain,
+// barrier, one system release, signal on row g, wait_epoch, one acquire,
+// copy-out, embedded host mark — is the byte kernel's, statement for
+// statement.
+struct typed_a2a_args {
+    a2a_args a;
+    typed_end se, re;
+    int force64;
+};
+
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void fused_alltoall_typed_kernel(typed_a2a_args ta) {
+    const a2a_args &a = ta.a;
+    const int t = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+    const bool st = ta.se.d.elems != nullptr, rt = ta.re.d.elems != nullptr;
+    const bool f64 = ta.force64 != 0;
+    int64_t lo, hi;
+    for (int k = 0; k < a.n; ++k) {  // my own block first, then peers rank+1, rank+2, ...
+        const int q = (a.rank + k) % a.n;
+        if (k == 0 && !a.self_copy) continue;
+        a2a_slice(a.scount[q], g, G, &lo, &hi);
+        const bool direct = k == 0 && !(st && rt);
+        char *s = const_cast<char *>(a.sbuf) + a.sdispl[q];
+        char *d = direct ? a.rbuf + a.rdispl[q]
+                         : (k == 0 ? a.mine : const_cast<char *>(a.peers.p[q])) + (int64_t)a.rank * a.slot;
+        if (st) typed_pipe_copy<false>(ta.se, s, d, lo, hi, a.scount[q], NT && k != 0, f64);
+        else if (direct && rt) typed_pipe_copy<true>(ta.re, d, s, lo, hi, a.scount[q], false, f64);
+        else pipe_copy(s, d, lo, hi, NT && k != 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) sys_release();
+    __syncthreads();
+    __shared__ int gave_up;
+    if (t == 0) gave_up = 0;
+    __syncthreads();
+    if (t < a.n && t != a.rank) {
+        __hip_atomic_store(a.peer_flags.p[t] + g * kMaxRanks + a.rank, a.epoch, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!wait_epoch(a.flags + g * kMaxRanks + t, a.epoch, a.err, a.timeout_ticks,
+                        a.flags + kAbortWord))
+            gave_up = 1;
+    }
+    __syncthreads();
+    if (gave_up) return;  // a peer never arrived: its slot holds nothing of this call
+    acquire_once();
+    for (int p = 0; p < a.n; ++p) {
+        if (p == a.rank && !(a.self_copy && st && rt)) continue;
+        a2a_slice(a.rcount[p], g, G, &lo, &hi);
+        char *s = a.mine + (int64_t)p * a.slot;
+        if (rt) typed_pipe_copy<true>(ta.re, a.rbuf + a.rdispl[p], s, lo, hi, a.rcount[p], false, f64);
+        else pipe_copy(s, a.rbuf + a.rdispl[p], lo, hi, false);
     }
     if (a.mark) {  // the host-observed completion, by the last workgroup
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -55,6 +55,11 @@ typedef struct mca_coll_rocm_module_t {
      * blocking reductions whose tuned algorithm the device path does not
      * run (ROCM_TUNED_* bits) stay with the saved functions */
     int tuned_decline;
+#ifdef ROCM_HAVE_TYPED_XCH
+    /* exchange collectives that handed a non-contiguous device operand to a
+     * library *_typed entry point as it is (tests tell it from the packed path) */
+    int typed_calls;
+#endif
 } mca_coll_rocm_module_t;
 
 enum { ROCM_TUNED_ALLREDUCE = 1, ROCM_TUNED_REDUCE = 2, ROCM_TUNED_RS = 4, ROCM_TUNED_RSB = 8 };
@@ -258,6 +263,15 @@ ROCM_DECLARE_FORMS(gather, ROCM_ROOTED_PARAMS)
 ROCM_DECLARE_FORMS(scatter, ROCM_ROOTED_PARAMS)
 ROCM_DECLARE_FORMS(gatherv, ROCM_GATHERV_PARAMS)
 ROCM_DECLARE_FORMS(scatterv, ROCM_SCATTERV_PARAMS)
+#endif
+
+/* ROCM_HAVE_TYPED_XCH, defined by the build (off by default): the twenty-one
+ * slots above hand a non-contiguous device operand whose datatype has a
+ * device program (common/rocm's opal_rocm_device_ddt) to the library's
+ * *_typed entry points as it is, with no packed copy through host memory.
+ * It needs both groups of slots and links opal_rocm_device_ddt. */
+#if defined(ROCM_HAVE_TYPED_XCH) && !(defined(ROCM_HAVE_ALLTOALL) && defined(ROCM_HAVE_GATHER))
+#error "ROCM_HAVE_TYPED_XCH needs the alltoall and the gather slots"
 #endif
 
 END_C_DECLS

@@ -254,6 +254,9 @@ static void rocm_module_construct(mca_coll_rocm_module_t *m)
     m->streak_dev = m->streak_host = 0;
     m->since_check = m->mismatched = 0;
     m->tuned_decline = 0;
+#ifdef ROCM_HAVE_TYPED_XCH
+    m->typed_calls = 0;
+#endif
     for (int k = 0; k < 2; ++k) {
         m->dstage[k] = m->hstage[k] = NULL;
         m->dstage_bytes[k] = m->hstage_bytes[k] = 0;
@@ -557,12 +560,25 @@ typedef struct {
     struct ompi_datatype_t *dtype;
     int in, out;
     void *use;
-    int how;        /* 0 as is, 1 byte copy of the typed span, 2 packed */
+    int how;        /* 0 as is, 1 byte copy of the typed span, 2 packed, 3 typed */
     ptrdiff_t gap;  /* true lower bound of the span */
     size_t bytes;
     char *hbuf;     /* packed: the host side of the pack / unpack */
     int contig;
+#ifdef ROCM_HAVE_TYPED_XCH
+    /* how == 3: a non-contiguous device operand goes to the library as it is,
+     * with its device program; only the exchange collectives ask for it */
+    int typed_ok;
+    const ompi_amd_ddt_t *ddt;
+#endif
 } rocm_operand_t;
+
+#ifdef ROCM_HAVE_TYPED_XCH
+/* common/rocm's device program of a datatype, NULL when it has none
+ * (opal_datatype_rocm.h; osc/rocm uses it the same way) */
+struct opal_datatype_t;
+const ompi_amd_ddt_t *opal_rocm_device_ddt(const struct opal_datatype_t *dt);
+#endif
 
 /* Staging memory of one operand slot: the module's grow-only buffers for
  * blocking calls, a nonblocking request's own for its lifetime. */
@@ -637,6 +653,14 @@ static int rocm_stage_with(rocm_buf_fn get, void *ctx, rocm_operand_t *o, int n,
         contig = ompi_datatype_is_contiguous_memory_layout(x->dtype, (int) x->count);
         if (to_dev ? (is_dev && contig) : !is_dev) continue;
         x->contig = contig;
+#ifdef ROCM_HAVE_TYPED_XCH
+        /* the library walks the datatype itself: nothing to stage, in or out */
+        if (to_dev && !contig && is_dev && x->typed_ok &&
+            NULL != (x->ddt = opal_rocm_device_ddt((const struct opal_datatype_t *) x->dtype))) {
+            x->how = 3;
+            continue;
+        }
+#endif
         if (to_dev && !contig) {
             size_t size = 0;
             (void) ompi_datatype_type_size(x->dtype, &size);
@@ -672,7 +696,7 @@ static int rocm_unstage_ops(const rocm_operand_t *o, int n, int rc)
 {
     for (int i = 0; OMPI_SUCCESS == rc && i < n; ++i) {
         const rocm_operand_t *x = &o[i];
-        if (!x->out || 0 == x->how) continue;
+        if (!x->out || 0 == x->how || 3 == x->how) continue;
         if (1 == x->how) {
             if (OMPI_AMD_SUCCESS != ompi_amd_memcpy((char *) x->user + x->gap,
                                                     (char *) x->use + x->gap, x->bytes)) {
@@ -1732,6 +1756,54 @@ int mca_coll_rocm_exscan_init(const void *sbuf, void *rbuf, int count, struct om
                                  (mca_coll_rocm_module_t *) module, 1);
 }
 
+#ifdef ROCM_HAVE_TYPED_XCH
+/* ------------------------------------------- the exchange collectives, typed
+ * With ROCM_HAVE_TYPED_XCH the device path of the twenty-one slots below
+ * calls the library's *_typed entry points.  An operand rocm_stage left as
+ * it is with its device program (how == 3) goes with that program, counts in
+ * elements and displacements in extents; every other operand goes as bytes
+ * (datatype NULL), contiguous or packed exactly as without the macro.  EVERY
+ * rank calls the typed entry point, also one whose operands are all bytes:
+ * a typed call's landing slots hold the packed stream at phase 0 where the
+ * byte forms follow the block's offset, and a rank cannot see whether a peer
+ * passed a datatype (matching signatures allow a vector on one rank and a
+ * contiguous type on the next).  Which operand is typed stays a local choice. */
+static void xch_typed_ok(rocm_operand_t *o)
+{
+    o[0].typed_ok = o[1].typed_ok = 1;
+    o[0].ddt = o[1].ddt = NULL;
+}
+
+static const ompi_amd_ddt_t *xch_ddt(const rocm_operand_t *x)
+{
+    return 3 == x->how ? x->ddt : NULL;
+}
+
+/* `elems` elements of `size` bytes as the typed entry point counts them */
+static size_t xch_count(const rocm_operand_t *x, size_t elems, size_t size)
+{
+    return 3 == x->how ? elems : elems * size;
+}
+
+static void xch_typed_note(mca_coll_rocm_module_t *m, const rocm_operand_t *o)
+{
+    if (3 == o[0].how || 3 == o[1].how) m->typed_calls++;
+}
+/* the library's entry point of a collective in each form, and the two
+ * datatypes that follow its operands */
+#define XCH_FN(name) ompi_amd_##name##_typed
+#define XCH_FN_I(name) ompi_amd_i##name##_typed
+#define XCH_FN_INIT(name) ompi_amd_##name##_typed_init
+#define XCH_TYPES(o) , xch_ddt(&(o)[0]), xch_ddt(&(o)[1])
+#define XCH_COUNT(x, elems, dtype) xch_count(x, (size_t) (elems), xch_type_size(dtype))
+#else
+#define XCH_COUNT(x, elems, dtype) ((size_t) (elems) * xch_type_size(dtype))
+#define XCH_FN(name) ompi_amd_##name
+#define XCH_FN_I(name) ompi_amd_i##name
+#define XCH_FN_INIT(name) ompi_amd_##name##_init
+#define XCH_TYPES(o)
+#endif
+
 #ifdef ROCM_HAVE_ALLTOALL
 /* ------------------------------------------------------------- alltoall(v)
  * MPI_Alltoall / MPI_Alltoallv and their nonblocking and persistent forms
@@ -1770,6 +1842,9 @@ static int rocm_alltoall_common(const void *sbuf, int scount, struct ompi_dataty
     ompi_request_t *inner = NULL;
     size_t ssize = 0, rsize = 0, bytes;
     int path, rc, ok, same;
+#ifdef ROCM_HAVE_TYPED_XCH
+    xch_typed_ok(o);
+#endif
     (void) ompi_datatype_type_size(rdtype, &rsize);
     if (!inplace) (void) ompi_datatype_type_size(sdtype, &ssize);
     bytes = rsize * (size_t) rcount;
@@ -1796,6 +1871,24 @@ static int rocm_alltoall_common(const void *sbuf, int scount, struct ompi_dataty
         return rocm_saved_post(rc, inner, st, comm, request);
     }
     sbuf = inplace ? (const void *) 1 : o[0].use;
+#ifdef ROCM_HAVE_TYPED_XCH
+    {
+        const ompi_amd_ddt_t *sddt = xch_ddt(&o[0]), *rddt = xch_ddt(&o[1]);
+        const size_t sc = inplace ? 0 : xch_count(&o[0], (size_t) scount, ssize);
+        const size_t rcn = xch_count(&o[1], (size_t) rcount, rsize);
+        xch_typed_note(m, o);
+        if (A2A_BLOCKING == form) {
+            rc = ompi_amd_alltoall_typed(m->dev_comm, sbuf, o[1].use, sc, rcn, sddt, rddt, NULL);
+            return rocm_dev_finish(m, o, 2, rc);
+        }
+        if (A2A_NONBLOCKING == form) {
+            rc = ompi_amd_ialltoall_typed(m->dev_comm, sbuf, o[1].use, sc, rcn, sddt, rddt, NULL, &nb);
+            return rocm_nb_post(rc, nb, st, comm, request);
+        }
+        rc = ompi_amd_alltoall_typed_init(m->dev_comm, sbuf, o[1].use, sc, rcn, sddt, rddt, &plan);
+        return rocm_wrap_plan(rc, plan, st, comm, request);
+    }
+#else
     if (A2A_BLOCKING == form) {
         rc = ompi_amd_alltoall(m->dev_comm, sbuf, o[1].use, bytes, NULL);
         return rocm_dev_finish(m, o, 2, rc);
@@ -1806,6 +1899,7 @@ static int rocm_alltoall_common(const void *sbuf, int scount, struct ompi_dataty
     }
     rc = ompi_amd_alltoall_init(m->dev_comm, sbuf, o[1].use, bytes, &plan);
     return rocm_wrap_plan(rc, plan, st, comm, request);
+#endif
 }
 
 #endif /* ROCM_HAVE_ALLTOALL */
@@ -1830,6 +1924,15 @@ static void a2av_bytes(const rocm_operand_t *x, struct ompi_datatype_t *dtype, c
     ptrdiff_t lb, ext;
     (void) ompi_datatype_type_size(dtype, &size);
     (void) ompi_datatype_get_extent(dtype, &lb, &ext);
+#ifdef ROCM_HAVE_TYPED_XCH
+    if (3 == x->how) { /* the typed entry points take elements and extents */
+        for (int p = 0; p < n; ++p) {
+            bc[p] = (size_t) counts[p];
+            bd[p] = (size_t) disps[p];
+        }
+        return;
+    }
+#endif
     for (int p = 0; p < n; ++p) {
         bc[p] = (size_t) counts[p] * size;
         bd[p] = (size_t) disps[p] * (2 == x->how ? size : (size_t) ext);
@@ -1859,6 +1962,9 @@ static int rocm_alltoallv_common(const void *sbuf, const int *scounts, const int
     size_t sc[OMPI_AMD_MAX_RANKS], sd[OMPI_AMD_MAX_RANKS], rc_[OMPI_AMD_MAX_RANKS],
         rd[OMPI_AMD_MAX_RANKS];
     int path, rc, ok;
+#ifdef ROCM_HAVE_TYPED_XCH
+    xch_typed_ok(o);
+#endif
     ok = ompi_datatype_is_contiguous_memory_layout(rdtype, (int) rspan) && (0 == rspan || dev(rbuf)) &&
          (inplace || 0 == sspan ||
           (dev(sbuf) && ompi_datatype_is_contiguous_memory_layout(sdtype, (int) sspan)));
@@ -1882,18 +1988,21 @@ static int rocm_alltoallv_common(const void *sbuf, const int *scounts, const int
     a2av_bytes(&o[1], rdtype, rcounts, rdisps, n, rc_, rd);
     if (!inplace) a2av_bytes(&o[0], sdtype, scounts, sdisps, n, sc, sd);
     sbuf = inplace ? (const void *) 1 : o[0].use;
+#ifdef ROCM_HAVE_TYPED_XCH
+    xch_typed_note(m, o);
+#endif
     if (A2A_BLOCKING == form) {
-        rc = ompi_amd_alltoallv(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
-                                rc_, rd, NULL);
+        rc = XCH_FN(alltoallv)(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                               rc_, rd XCH_TYPES(o), NULL);
         return rocm_dev_finish(m, o, 2, rc);
     }
     if (A2A_NONBLOCKING == form) {
-        rc = ompi_amd_ialltoallv(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
-                                 rc_, rd, NULL, &nb);
+        rc = XCH_FN_I(alltoallv)(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                                 rc_, rd XCH_TYPES(o), NULL, &nb);
         return rocm_nb_post(rc, nb, st, comm, request);
     }
-    rc = ompi_amd_alltoallv_init(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
-                                 rc_, rd, &plan);
+    rc = XCH_FN_INIT(alltoallv)(m->dev_comm, sbuf, inplace ? NULL : sc, inplace ? NULL : sd, o[1].use,
+                                rc_, rd XCH_TYPES(o), &plan);
     return rocm_wrap_plan(rc, plan, st, comm, request);
 }
 
@@ -1979,9 +2088,11 @@ enum { XCH_BLOCKING = 0, XCH_NONBLOCKING = 1, XCH_PERSISTENT = 2 };
                : m->c_coll.coll_##X##_init(__VA_ARGS__, comm, info, &x.inner,                  \
                                            m->c_coll.coll_##X##_init_module))
 #define XCH_DEVICE(X, ...)                                                                     \
-    (XCH_BLOCKING == form      ? ompi_amd_##X(m->dev_comm, __VA_ARGS__, NULL)                  \
-     : XCH_NONBLOCKING == form ? ompi_amd_i##X(m->dev_comm, __VA_ARGS__, NULL, &x.nb)          \
-                               : ompi_amd_##X##_init(m->dev_comm, __VA_ARGS__, &x.plan))
+    (XCH_BLOCKING == form                                                                      \
+         ? XCH_FN(X)(m->dev_comm, __VA_ARGS__ XCH_TYPES(x.o), NULL)                            \
+         : XCH_NONBLOCKING == form                                                             \
+               ? XCH_FN_I(X)(m->dev_comm, __VA_ARGS__ XCH_TYPES(x.o), NULL, &x.nb)             \
+               : XCH_FN_INIT(X)(m->dev_comm, __VA_ARGS__ XCH_TYPES(x.o), &x.plan))
 
 struct rocm_xch {
     rocm_operand_t o[2];
@@ -1999,8 +2110,19 @@ static int rocm_xch_begin(mca_coll_rocm_module_t *m, int form, int uniform_ok, i
     x->nb = NULL;
     x->plan = NULL;
     x->inner = NULL;
+#ifdef ROCM_HAVE_TYPED_XCH
+    {
+        int rc;
+        xch_typed_ok(x->o);
+        rc = XCH_BLOCKING == form ? rocm_begin(m, uniform_ok, local_ok, x->o, 2, &x->path)
+                                  : rocm_nb_begin(m, uniform_ok, local_ok, x->o, 2, &x->st, &x->path);
+        if (OMPI_SUCCESS == rc && ROCM_DEVICE == x->path) xch_typed_note(m, x->o);
+        return rc;
+    }
+#else
     if (XCH_BLOCKING == form) return rocm_begin(m, uniform_ok, local_ok, x->o, 2, &x->path);
     return rocm_nb_begin(m, uniform_ok, local_ok, x->o, 2, &x->st, &x->path);
+#endif
 }
 
 /* what follows the saved function's / the library's return in each form */
@@ -2054,7 +2176,7 @@ static int rocm_allgatherv_common(ROCM_AGV_PARAMS, struct ompi_communicator_t *c
     } else {
         a2av_bytes(&x.o[1], rdtype, rcounts, disps, n, rc_, rd);
         sbuf = inplace ? (const void *) 1 : x.o[0].use;
-        rc = XCH_DEVICE(allgatherv, sbuf, inplace ? 0 : (size_t) scount * xch_type_size(sdtype),
+        rc = XCH_DEVICE(allgatherv, sbuf, inplace ? 0 : XCH_COUNT(&x.o[0], scount, sdtype),
                         x.o[1].use, rc_, rd);
     }
     return rocm_xch_end(m, form, rc, &x, comm, request);
@@ -2091,6 +2213,17 @@ static int rocm_rooted_common(int scatter, ROCM_ROOTED_PARAMS, struct ompi_commu
     if (ROCM_DEVICE != x.path) {
         rc = scatter ? XCH_SAVED(scatter, s, scount, sdtype, r, rcount, rdtype, root)
                      : XCH_SAVED(gather, s, scount, sdtype, r, rcount, rdtype, root);
+#ifdef ROCM_HAVE_TYPED_XCH
+    } else {
+        /* a count per side, each from its own datatype where that side is
+         * significant at this rank (0 where it is not) */
+        const size_t sc = selems ? XCH_COUNT(&x.o[0], scount, sdtype) : 0;
+        const size_t rcn = relems ? XCH_COUNT(&x.o[1], rcount, rdtype) : 0;
+        if (inplace && scatter) r = (void *) 1;
+        if (inplace && !scatter) s = (const void *) 1;
+        rc = scatter ? XCH_DEVICE(scatter, s, r, sc, rcn, root) : XCH_DEVICE(gather, s, r, sc, rcn, root);
+    }
+#else
     } else if (scatter) {
         if (inplace) r = (void *) 1;
         rc = XCH_DEVICE(scatter, s, r, bytes, root);
@@ -2098,6 +2231,7 @@ static int rocm_rooted_common(int scatter, ROCM_ROOTED_PARAMS, struct ompi_commu
         if (inplace) s = (const void *) 1;
         rc = XCH_DEVICE(gather, s, r, bytes, root);
     }
+#endif
     return rocm_xch_end(m, form, rc, &x, comm, request);
 }
 
@@ -2122,7 +2256,7 @@ static int rocm_rooted_v_common(int scatter, const void *sbuf, void *rbuf, int c
                            scatter ? nelems : span, scatter ? ndtype : wdtype, !scatter, 1}},
                          NULL, NULL, NULL, NULL, 0};
     size_t bc[OMPI_AMD_MAX_RANKS], bd[OMPI_AMD_MAX_RANKS];
-    const size_t nbytes = nelems * xch_type_size(ndtype);
+    size_t nbytes;  /* the narrow operand's count: bytes, or elements where it goes typed */
     const void *s;
     void *r;
     int rc = rocm_xch_begin(m, form, 1,
@@ -2137,6 +2271,7 @@ static int rocm_rooted_v_common(int scatter, const void *sbuf, void *rbuf, int c
                      : XCH_SAVED(gatherv, s, count, ndtype, r, counts, disps, wdtype, root);
         return rocm_xch_end(m, form, rc, &x, comm, request);
     }
+    nbytes = nelems ? XCH_COUNT(&x.o[scatter ? 1 : 0], nelems, ndtype) : 0;
     if (is_root) a2av_bytes(&x.o[scatter ? 0 : 1], wdtype, counts, disps, n, bc, bd);
     if (scatter) {
         if (inplace) r = (void *) 1;
