@@ -122,15 +122,16 @@ def typed_bounds(dt, count):
     return lo + min(0, last), hi + max(0, last)
 
 
-def rand_layout(rng):
-    """(class name, datatype) of one of LAYOUT_CLASSES — the layouts
+def rand_layout(rng, cls=None):
+    """(class name, datatype) of one of LAYOUT_CLASSES (cls: of that one) — the layouts
     rand_type cannot draw: negative strides, typemap order != address order,
     runs below the origin, resized extents smaller than the span
     (interleaved instances), larger, negative, or overlapping.  The type's
     `max_count` (None: any) is the largest count at which instances do not
     overlap; `stacked` types overlap at every count > 1 (send only)."""
-    r = rng.random()
-    cls = "stacked" if r < 0.075 else LAYOUT_CLASSES[int((r - 0.075) / 0.925 * 6)]
+    if cls is None:
+        r = rng.random()
+        cls = "stacked" if r < 0.075 else LAYOUT_CLASSES[int((r - 0.075) / 0.925 * 6)]
     max_count = None
     if cls == "negstride":
         dt = _negstride(rng)

@@ -20,21 +20,27 @@ from test_coll_gpu import run_ranks  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "typed_worker.py")
-CASES = {"shapes", "mixed", "inplace", "forms", "force64", "interleave"}
+CASES = {"shapes", "mixed", "inplace", "forms", "force64", "interleave", "layouts"}
 NAMES = ("alltoall", "alltoallv", "allgatherv", "gather", "scatter", "gatherv", "scatterv")
 
 
 @pytest.mark.parametrize("n", [2, 3, 4, 8])
 def test_typed_ranks(n):
     outs = run_ranks(n, timeout=240, worker=WORKER, tag="typed")
-    failures = []
+    failures, granules, seconds = [], set(), {}
     for r, (rc, out) in enumerate(outs):
         lines = [json.loads(ln) for ln in out.splitlines() if ln.startswith("{")]
+        for ln in lines:
+            granules |= set(ln.get("granules", []))
+            seconds[ln["case"]] = max(seconds.get(ln["case"], 0), ln["s"])
         bad = [ln for ln in lines if not ln["ok"]]
         missing = CASES - {ln["case"] for ln in lines}
         if rc != 0 or bad or missing:
             failures.append((r, rc, bad[:3], sorted(missing), out[-1500:] if rc not in (0, 1) or not lines else ""))
     assert not failures, failures
+    print(f"typed worker N = {n}: seconds per case (slowest rank) {seconds}")
+    # the generated calls of `layouts` took every granule on some rank
+    assert granules == {1, 2, 4, 8, 16}, granules
 
 
 def _comm(tag):
@@ -80,6 +86,7 @@ def test_typed_single_rank():
 
 def test_typed_bad_params():
     """With a live communicator: every argument error of the header comment
+    (a datatype with a negative extent on either side among them)
     returns BAD_PARAM from all three forms and no request or plan comes back;
     nothing reaches the device (comm.error() stays 0, no path counter moves);
     zero-element calls with NULL buffers are legal."""
@@ -93,6 +100,9 @@ def test_typed_bad_params():
         # the Datatype objects stay referenced: dropping one frees its device program
         V, W = dt.from_runs("v12", [(0, 4)], 12), dt.from_runs("w", [(0, 2), (4, 4)], 8)
         v, w = V.commit()._handle, W.commit()._handle   # sizes 4 and 6
+        # v12's typemap with a negative extent: displacement * extent is a size_t, so it is refused
+        NEG = dt.type_create_resized(V, 0, -12)
+        neg = NEG.commit()._handle
         cnt, dsp = (ctypes.c_size_t * 1)(3), (ctypes.c_size_t * 1)(0)
         zero = (ctypes.c_size_t * 1)(0)
         none = ctypes.POINTER(ctypes.c_size_t)()
@@ -124,6 +134,8 @@ def test_typed_bad_params():
                    "allgatherv": (None, 0, None, zero, dsp, v, v), "gather": (None, None, 0, 0, 0, v, v),
                    "scatter": (None, None, 0, 0, 0, v, v), "gatherv": (None, 0, None, zero, dsp, 0, v, v),
                    "scatterv": (None, zero, dsp, None, 0, 0, v, v)}
+        for name in NAMES:
+            bad[name] += [good[name][:-2] + (neg, v), good[name][:-2] + (v, neg), good[name][:-2] + (neg, neg)]
         for name in NAMES:
             f, fi, fp = (getattr(lib, f"ompi_amd_{x}") for x in
                          (name + "_typed", "i" + name + "_typed", name + "_typed_init"))

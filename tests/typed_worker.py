@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+import typed_random as tr  # noqa: E402
 from gather_worker import Buf, PREFILL, force  # noqa: E402
 from ompi_amd import coll  # noqa: E402
 from ompi_amd import datatype as dt  # noqa: E402
@@ -257,6 +258,94 @@ class Call:
         return True, ""
 
 
+class OBuf:
+    """A whole buffer image of a generated call (typed_random.Case: the 64
+    guard bytes on each side and every byte the datatype skips included) on
+    the device, with the buffer ORIGIN `off` bytes past a 256-B boundary:
+    a datatype may own bytes below the pointer the call gets."""
+
+    def __init__(self, image: np.ndarray, origin: int, off: int):
+        self.n = image.size
+        self.t = torch.empty(self.n + 768, dtype=torch.uint8, device="cuda")
+        self.at = (off - origin - self.t.data_ptr()) % 256 + 256
+        self.ptr = self.t.data_ptr() + self.at + origin
+        self.set(image)
+
+    def set(self, image: np.ndarray):
+        self.want = image
+        self.t[self.at:self.at + self.n].copy_(torch.from_numpy(image))
+
+    def expect(self, image: np.ndarray):
+        self.want = image
+
+    def check(self, what):
+        got = self.t[self.at:self.at + self.n].cpu().numpy()
+        if np.array_equal(got, self.want):
+            return True, ""
+        bad = np.flatnonzero(got != self.want)
+        return False, (f"{what}: {bad.size}/{got.size} bytes differ, first at image byte {int(bad[0])} "
+                       f"(got {int(got[bad[0]])} want {int(self.want[bad[0]])}), last at {int(bad[-1])}")
+
+
+class GenCall:
+    """A typed_random.Case on this rank: its buffers, operands and checks."""
+
+    def __init__(self, comm, case):
+        self.comm, self.case, self.me = comm, case, comm.rank
+        me = self.me
+        self.sbuf = OBuf(case.send_image(me), case.origin(0, me), case.soff[me]) \
+            if case.sends(me) and not case.inplace else None
+        self.rbuf = OBuf(case.prefill(me), case.origin(1, me), case.roff[me]) if case.recvs(me) else None
+        if self.rbuf:
+            self.rbuf.expect(case.expected(me, oracle))
+
+    def refill(self, epoch):
+        """Other input and prefill in the same buffers (persistent starts)."""
+        if self.sbuf:
+            self.sbuf.set(self.case.send_image(self.me, epoch))
+        if self.rbuf:
+            self.rbuf.set(self.case.prefill(self.me, epoch))
+            self.rbuf.expect(self.case.expected(self.me, oracle, epoch))
+
+    def reset(self):
+        """The receive buffer back to its prefill (the same call again)."""
+        if self.rbuf:
+            want = self.rbuf.want
+            self.rbuf.set(self.case.prefill(self.me))
+            self.rbuf.expect(want)
+
+    def moves(self):
+        """Does this rank walk a datatype in this call?"""
+        c, me = self.case, self.me
+        return (c.st[me] is not None and any(c.sc[me])) or (c.rt[me] is not None and any(c.rc[me]))
+
+    def args(self):
+        s = coll.IN_PLACE if self.case.inplace else (self.sbuf.ptr if self.sbuf else None)
+        return self.case.args(self.me, s, self.rbuf.ptr if self.rbuf else None)
+
+    def init(self):
+        return getattr(self.comm, self.case.kind + "_typed_init")(*self.args())
+
+    def run(self, form="blocking"):
+        if form == "blocking":
+            getattr(self.comm, self.case.kind + "_typed")(*self.args(), blocking=True)
+        else:
+            r = getattr(self.comm, "i" + self.case.kind + "_typed")(*self.args())
+            r.wait()
+            r.free()
+        return self.check()
+
+    def check(self):
+        if self.comm.error():
+            return False, f"device error {self.comm.error()}: {self.case.what()}"
+        for name, b in (("rbuf", self.rbuf), ("sbuf", self.sbuf)):   # a source comes back unchanged
+            if b is not None:
+                ok, msg = b.check(f"{self.case.what()} {name}")
+                if not ok:
+                    return ok, msg
+        return True, ""
+
+
 def typed_paths(comm):
     return tuple(comm.get_param(k) for k in ("typed_fused", "typed_staged", "typed_landing"))
 
@@ -462,8 +551,56 @@ def case_interleave(comm, rank, n, T):
     return True, ""
 
 
+EXTRA = {}   # case name -> further fields of its JSON line
+
+
+def case_layouts(comm, rank, n, T):
+    """Generated calls (typed_random.worker_case) on each forced path: every
+    rank with datatypes of its own, all seven kinds, every root at N = 3,
+    ragged rows with a zero, in place, more than 16 KiB per pair, passes of
+    256 B, two full trips of byte granules per fused workgroup, the 64-bit
+    walk.  N = 8 runs the shorter list typed_random.WORKER_SEEDS_N8 (the kinds
+    of seeds 0-4 and the four directed seeds).  Reports the granules this
+    rank's launches took."""
+    gs = set()
+    try:
+        for path in range(3):
+            force(comm, path)
+            for s in tr.WORKER_SEEDS_N8 if n == 8 else range(tr.WORKER_SEEDS):
+                case, meta = tr.worker_case(s, n, path)
+                chunked = meta["chunk"] and path == 2
+                comm.set_param("alltoall_chunk", meta["chunk"] if chunked else 0)
+                comm.set_param("typed_force64", meta["force64"])
+                x = GenCall(comm, case)
+                before, w0 = typed_paths(comm), comm.get_param("typed_walk64")
+                p0 = comm.get_param("alltoall_passes") + comm.get_param("gather_passes")
+                ok, msg = x.run("post" if s % 4 == 3 else "blocking")
+                if ok:
+                    ok, msg = took(comm, before, path)
+                g = comm.get_param("typed_granule")
+                print(f"# layouts path {path} seed {s}: typed_granule {g} {case.what()}", flush=True)
+                if x.moves():
+                    gs.add(g)
+                    if ok and meta["G"] and g != meta["G"]:
+                        ok, msg = False, f"typed_granule {g}, expected {meta['G']}"
+                    if ok and meta["force64"] and comm.get_param("typed_walk64") == w0:
+                        ok, msg = False, "typed_walk64 did not move"
+                passes = comm.get_param("alltoall_passes") + comm.get_param("gather_passes") - p0
+                most = max(max(row) for row in case.B)
+                if ok and chunked and passes != -(-most // 256):
+                    ok, msg = False, f"{passes} passes, expected {-(-most // 256)}"
+                if not ok:
+                    return False, f"path {path} seed {s}: {msg}"
+    finally:
+        comm.set_param("alltoall_chunk", 0)
+        comm.set_param("typed_force64", 0)
+        force(comm, None)
+        EXTRA["layouts"] = {"granules": sorted(gs)}
+    return True, ""
+
+
 CASES = [("shapes", case_shapes), ("mixed", case_mixed), ("inplace", case_inplace), ("forms", case_forms),
-         ("force64", case_force64), ("interleave", case_interleave)]
+         ("force64", case_force64), ("interleave", case_interleave), ("layouts", case_layouts)]
 
 
 def report(rank, n, obj):
@@ -496,7 +633,7 @@ def main():
         except Exception as e:  # noqa: BLE001 — a library error is the case's failure
             ok, msg = False, f"{type(e).__name__}: {e}"
         report(rank, n, {"rank": rank, "case": name, "ok": bool(ok), "msg": msg,
-                         "s": round(time.time() - t0, 3)})
+                         "s": round(time.time() - t0, 3), **EXTRA.pop(name, {})})
         ok_all = ok_all and ok
         if comm.error():  # the communicator is unusable after a device error
             break
