@@ -513,6 +513,41 @@ OMPI_AMD_TYPED_FORMS_(scatterv, const void *sbuf, const size_t *scounts, const s
 #undef OMPI_AMD_TYPED_FORMS_
 #undef OMPI_AMD_TYPES_
 
+/* MPI_Alltoallw on the device: the exchange above with ONE DATATYPE PER PEER
+ * on either side.  sddts / rddts have `size` entries (NULL entry: bytes);
+ * scounts[q] / rcounts[p] are ELEMENTS of that peer's datatype, and — MPI's
+ * rule for alltoallw, unlike the _typed forms above — sdispls / rdispls are
+ * BYTES, not extents.  A pair with count 0 ignores its datatype and
+ * displacement.  MPI_IN_PLACE is sbuf == rbuf or (void *)1: the receive side
+ * then describes both directions and the send arrays may be NULL.  All
+ * arrays are copied at post / init; the datatypes are kept by reference as
+ * the _typed forms keep them.  Same three paths, thresholds and slots chosen
+ * from PACKED bytes; the largest pair is agreed as alltoallv agrees it, so
+ * alltoallw_init is collective.  Plans are kind 4.
+ *   OMPI_AMD_ERR_BAD_PARAM, before any device work and with no request or
+ * plan coming back: everything alltoallv_typed refuses (a NULL count or
+ * displacement array or buffer that is needed, a datatype that is no valid
+ * device program); a NULL datatype array (sddts only when not in place); own
+ * pair packed bytes that differ between the two sides when not in place
+ * (scounts[rank] * size(sddts[rank]) != rcounts[rank] * size(rddts[rank])); a
+ * negative extent in any entry that moves data; count * size past SIZE_MAX.
+ *   get_param "alltoallw_calls" counts these calls (they move the typed_* and
+ * alltoall_* counters too) and "alltoallw_lds_programs" their launches that
+ * ran with every element program staged in LDS. */
+int ompi_amd_alltoallw(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                       const size_t *sdispls, const ompi_amd_ddt_t *const *sddts, void *rbuf,
+                       const size_t *rcounts, const size_t *rdispls,
+                       const ompi_amd_ddt_t *const *rddts, void *stream);
+int ompi_amd_ialltoallw(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                        const size_t *sdispls, const ompi_amd_ddt_t *const *sddts, void *rbuf,
+                        const size_t *rcounts, const size_t *rdispls,
+                        const ompi_amd_ddt_t *const *rddts, void *stream,
+                        ompi_amd_request_t **request);
+int ompi_amd_alltoallw_init(ompi_amd_comm_t *comm, const void *sbuf, const size_t *scounts,
+                            const size_t *sdispls, const ompi_amd_ddt_t *const *sddts, void *rbuf,
+                            const size_t *rcounts, const size_t *rdispls,
+                            const ompi_amd_ddt_t *const *rddts, ompi_amd_plan_t **plan);
+
 #ifdef __cplusplus
 }
 #endif

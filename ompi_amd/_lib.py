@@ -276,6 +276,13 @@ PROTOTYPES = [
     for pre, post, tail in [("", "", [_C.c_void_p]), ("i", "", [_C.c_void_p, _C.POINTER(_C.c_void_p)]),
                             ("", "_init", [_C.POINTER(_C.c_void_p)])]
 ] + [
+    # alltoallw: alltoallv's operands with an array of datatype handles per side
+    (f"ompi_amd_{pre}alltoallw{post}", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_void_p),
+      _C.c_void_p, _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_size_t), _C.POINTER(_C.c_void_p)] + tail)
+    for pre, post, tail in [("", "", [_C.c_void_p]), ("i", "", [_C.c_void_p, _C.POINTER(_C.c_void_p)]),
+                            ("", "_init", [_C.POINTER(_C.c_void_p)])]
+] + [
     # point-to-point (include/ompi_amd_p2p.h)
     ("ompi_amd_isend", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,

@@ -372,6 +372,42 @@ class Communicator:
     def _rooted_t(self, sbuf, rbuf, scount, rcount, root):
         return (_optr(sbuf), _optr(rbuf), int(scount), int(rcount), root)
 
+    # -- alltoallw: one datatype per peer ---------------------------------------
+    # sddts / rddts are lists of `size` Datatype objects (None entry: bytes).
+    # Counts are elements of that peer's datatype; displacements are BYTES
+    # (MPI's rule for alltoallw, unlike the _typed forms).  sbuf IN_PLACE: the
+    # receive side describes both directions and the send lists may be None.
+    # A request or plan keeps the lists' datatypes alive, as the typed forms.
+    def _ddts(self, types):
+        if types is None:
+            return ctypes.POINTER(ctypes.c_void_p)()
+        return (ctypes.c_void_p * len(types))(*[self._ddt(t) for t in types])
+
+    def _xch_w(self, form, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts, stream=None,
+               blocking=False):
+        args = (_optr(sbuf), self._osizes(scounts), self._osizes(sdispls), self._ddts(sddts),
+                _optr(rbuf), self._osizes(rcounts), self._osizes(rdispls), self._ddts(rddts))
+        h = self._xch("alltoallw", form, args, stream, blocking)
+        if h is not None:
+            h._types = (sddts, rddts)
+        return h
+
+    def alltoallw(self, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts, stream=None,
+                  blocking: bool = False) -> None:
+        """MPI_Alltoallw: scounts[q] elements of sddts[q] at byte sdispls[q]
+        of sbuf go to rank q, which receives them as rcounts[p] elements of
+        its rddts[p] at byte rdispls[p] of its rbuf."""
+        self._xch_w(0, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts, stream, blocking)
+
+    def ialltoallw(self, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts,
+                   stream=None) -> "Request":
+        return self._xch_w(1, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts, stream)
+
+    def alltoallw_init(self, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts) -> "Plan":
+        """MPI_Alltoallw_init: collective (the ranks agree on the largest
+        pair once); the starts make no host rendezvous."""
+        return self._xch_w(2, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts)
+
     # -- nonblocking forms (coll.h:261-410) -----------------------------------
     def ialltoall(self, sbuf, rbuf, nbytes: int, stream=None) -> "Request":
         h = ctypes.c_void_p()

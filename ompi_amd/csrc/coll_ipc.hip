@@ -380,6 +380,30 @@ struct shadow_set {
 // repeated rows; `coll` keeps their counters, their fused
 // kernel and their landing layout apart.
 enum { XCH_ALLTOALL = 0, XCH_ALLGATHERV = 1, XCH_GATHER = 2, XCH_SCATTER = 3 };
+
+// The datatypes of one alltoallw, out of line: a2a_call
+// carries a pointer, and a plan's starts share one.  View and switch [q],
+// q < N, are of what this rank sends to q, [N + p] of what it receives from
+// p (on false: that pair moves bytes).  `tab` is the table as the kernels
+// read it; `dev` its copy in device memory: a plan's own, uploaded at init
+// (owned), or the ring slot of the call being launched.
+constexpr int kA2awRing = 8;  // per-call tables: as many as the rendezvous ring has tickets
+struct a2aw_types {
+    std::vector<ddt_view> v;
+    std::vector<uint8_t> on;
+    a2aw_table tab{};
+    const a2aw_table *dev = nullptr;
+    bool owned = false;
+    // where a plan's table goes back to: the communicator's w_free, so a plan
+    // is freed before its communicator (as its request and mark words assume).
+    // No kernel reads the table by then: ompi_amd_plan_free waits for the last
+    // start's request (ompi_amd_request_free) before it deletes the plan.
+    std::vector<a2aw_table *> *pool = nullptr;
+    ~a2aw_types() {
+        if (owned && pool) pool->push_back(const_cast<a2aw_table *>(dev));
+    }
+};
+
 struct a2a_call {
     const char *sbuf;
     char *rbuf;
@@ -396,6 +420,8 @@ struct a2a_call {
     // (displacement * extent) and ph[] is 0.
     bool st, rt;
     ddt_view sv, rv;
+    // alltoallw: one datatype per peer and side instead (st / rt stay false)
+    std::shared_ptr<a2aw_types> w;
 };
 
 // A nonblocking collective posted but not launched yet.  Device work must
@@ -651,6 +677,19 @@ struct ompi_amd_comm {
     int64_t typed_granule = 0;
     int64_t typed_walk64 = 0;
     int typed_force64 = 0;
+    // alltoallw: its calls, and its launches that ran with
+    // every element program staged in LDS.  A call's table goes from pinned
+    // slot w_seq % kA2awRing to the same device slot by one async copy on the
+    // call's stream; w_ev[slot] fires when that copy has read the pinned
+    // slot, which the host waits for before it fills the slot again.  Plans
+    // own a table each (w_all; w_free: those of freed plans).  All of it is
+    // allocated at the first alltoallw.
+    int64_t alltoallw_calls = 0;
+    int64_t alltoallw_lds = 0;
+    a2aw_table *w_ring_dev = nullptr, *w_ring_host = nullptr;
+    hipEvent_t w_ev[kA2awRing] = {};
+    uint64_t w_seq = 0;
+    std::vector<a2aw_table *> w_all, w_free;
     // param "copy_nt": 1 the copy and fold kernels store non-temporally —
     // measured no slower on one GPU at N = 2 / 4 / 8 (scatter, gather and fold
     // kernels 1-5 % faster) — 0 plain stores; -1 (default)
@@ -3406,6 +3445,11 @@ int ompi_amd_comm_destroy(ompi_amd_comm_t *c) {
     c->arena.clear();
     if (c->err_host) hip_ignore(hipHostFree(c->err_host));
     if (c->dbg_host) hip_ignore(hipHostFree(c->dbg_host));
+    if (c->w_ring_host) hip_ignore(hipHostFree(c->w_ring_host));  // the streams are drained (quiesce above)
+    if (c->w_ring_dev) hip_ignore(hipFree(c->w_ring_dev));
+    for (a2aw_table *t : c->w_all) hip_ignore(hipFree(t));
+    for (hipEvent_t e : c->w_ev)
+        if (e) hip_ignore(hipEventDestroy(e));
     for (int ph = 0; ph < 3; ++ph)
         for (auto &pr : c->ev_phase[ph]) {
             hip_ignore(hipEventDestroy(pr.first));
@@ -3666,6 +3710,8 @@ int ompi_amd_comm_get_param(const ompi_amd_comm_t *c, const char *key, int64_t *
     else if (!strcmp(key, "typed_granule")) *v = c->typed_granule;
     else if (!strcmp(key, "typed_walk64")) *v = c->typed_walk64;
     else if (!strcmp(key, "typed_force64")) *v = c->typed_force64;
+    else if (!strcmp(key, "alltoallw_calls")) *v = c->alltoallw_calls;
+    else if (!strcmp(key, "alltoallw_lds_programs")) *v = c->alltoallw_lds;
     else if (!strcmp(key, "copy_nt")) *v = c->copy_nt;
     else if (!strcmp(key, "copy_nt_fixed")) *v = c->copy_nt_fixed;
     else if (!strcmp(key, "unsafe_exports")) *v = c->unsafe_exports;
@@ -4852,7 +4898,13 @@ static size_t a2a_local_max(const ompi_amd_comm_t *c, const a2a_call &k) {
 }
 
 // ---- typed ends ----
-static bool a2a_typed(const a2a_call &k) { return k.st || k.rt; }
+static bool a2a_typed(const a2a_call &k) { return k.st || k.rt || k.w; }
+// is what I send to q / receive from p typed, and by which view (alltoallw:
+// the pair's own, end q / N + p of its table)
+static bool a2a_st(const a2a_call &k, int q) { return k.w ? k.w->on[q] != 0 : k.st; }
+static bool a2a_rt(const a2a_call &k, int p) { return k.w ? k.w->on[k.w->on.size() / 2 + p] != 0 : k.rt; }
+static const ddt_view &a2a_sv(const a2a_call &k, int q) { return k.w ? k.w->v[q] : k.sv; }
+static const ddt_view &a2a_rv(const a2a_call &k, int p) { return k.w ? k.w->v[k.w->v.size() / 2 + p] : k.rv; }
 
 static typed_end end_of(bool on, const ddt_view &v) {
     typed_end e{};
@@ -4886,23 +4938,128 @@ static void note_launch(ompi_amd_comm_t *c, const typed_note &tn) {
     if (tn.w64) ++c->typed_walk64;
 }
 
-static int launch_typed_copy(ompi_amd_comm_t *c, const a2a_call &k, tcp_jobs &jobs, hipStream_t s) {
+// ---- alltoallw's table ----
+// w->tab from w->v / w->on: the ends, and where each program sits in LDS when
+// the distinct programs together fit kA2awLdsElems.
+static void a2aw_fill(a2aw_types *w) {
+    a2aw_table &t = w->tab;
+    t = a2aw_table{};
+    const int ends = (int)w->v.size();
+    int used = 0;
+    for (int i = 0; i < ends; ++i) {
+        t.e[i] = end_of(w->on[i] != 0, w->v[i]);
+        t.lds_at[i] = -1;
+        if (!w->on[i]) continue;
+        for (int j = 0; j < i && t.lds_at[i] < 0; ++j)
+            if (w->on[j] && w->v[j].d.elems == w->v[i].d.elems) t.lds_at[i] = t.lds_at[j];
+        if (t.lds_at[i] < 0) {
+            t.lds_at[i] = used;
+            used += w->v[i].d.nelem;
+        }
+    }
+    for (int i = ends; i < 2 * kMaxRanks; ++i) t.lds_at[i] = -1;
+    t.lds_on = used > 0 && used <= kA2awLdsElems;
+    if (!t.lds_on)
+        for (int i = 0; i < ends; ++i) t.lds_at[i] = -1;
+}
+
+static int a2aw_ring(ompi_amd_comm_t *c) {
+    if (c->w_ring_dev) return OMPI_AMD_SUCCESS;
+    TRY(set_dev(c));
+    TRY(record_hip(hipHostMalloc((void **)&c->w_ring_host, kA2awRing * sizeof(a2aw_table), hipHostMallocDefault),
+                   "alltoallw table ring (pinned)"));
+    return record_hip(hipMalloc((void **)&c->w_ring_dev, kA2awRing * sizeof(a2aw_table)), "alltoallw table ring");
+}
+
+// The table of a call about to launch on s: a plan's is on the device
+// already; any other goes through the next ring slot, by one async copy on s
+// ahead of the call's kernels.  (A communicator's calls run in order on the
+// device whatever their streams, note_stream, so the device slot is free by
+// then; the pinned slot is free once its previous copy has run.)
+static int a2aw_upload(ompi_amd_comm_t *c, a2aw_types *w, hipStream_t s) {
+    if (w->owned) return OMPI_AMD_SUCCESS;
+    TRY(a2aw_ring(c));
+    note_stream(c, s);
+    const int slot = (int)(c->w_seq++ % kA2awRing);
+    hipEvent_t &ev = c->w_ev[slot];
+    if (!ev) TRY(record_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "alltoallw table event"));
+    else if (hipEventQuery(ev) != hipSuccess) {
+        (void)hipGetLastError();
+        TRY(record_hip(wait_event(ev), "alltoallw table slot"));
+    }
+    c->w_ring_host[slot] = w->tab;
+    TRY(record_hip(hipMemcpyAsync(c->w_ring_dev + slot, c->w_ring_host + slot, sizeof(a2aw_table),
+                                  hipMemcpyHostToDevice, s),
+                   "alltoallw table copy"));
+    TRY(record_hip(hipEventRecord(ev, s), "alltoallw table event"));
+    w->dev = c->w_ring_dev + slot;
+    return OMPI_AMD_SUCCESS;
+}
+
+// A plan's own table: from the pool of freed plans' or new, uploaded once
+// over a stream of its own (init is collective and rare; no start pays).
+static int a2aw_own(ompi_amd_comm_t *c, a2aw_types *w) {
+    TRY(set_dev(c));
+    TRY(a2aw_ring(c));
+    a2aw_table *d = nullptr;
+    if (!c->w_free.empty()) {
+        d = c->w_free.back();
+        c->w_free.pop_back();
+    } else {
+        TRY(record_hip(hipMalloc((void **)&d, sizeof(a2aw_table)), "alltoallw plan table"));
+        c->w_all.push_back(d);
+    }
+    w->dev = d;
+    w->owned = true;
+    w->pool = &c->w_free;
+    // through a pinned slot of the ring, as a call's table goes
+    const int slot = (int)(c->w_seq++ % kA2awRing);
+    if (c->w_ev[slot]) TRY(record_hip(wait_event(c->w_ev[slot]), "alltoallw table slot"));
+    c->w_ring_host[slot] = w->tab;
+    hipStream_t s = nullptr;
+    TRY(record_hip(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "alltoallw plan upload stream"));
+    hipError_t e = hipMemcpyAsync(d, c->w_ring_host + slot, sizeof(a2aw_table), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // a stream with this copy alone
+    hip_ignore(hipStreamDestroy(s));
+    return record_hip(e, "alltoallw plan table upload");
+}
+
+// end[i]: alltoallw only, the end of job i in the call's table
+static int launch_typed_copy(ompi_amd_comm_t *c, const a2a_call &k, tcp_jobs &jobs, const uint8_t *end,
+                             hipStream_t s) {
     if (jobs.n == 0) return OMPI_AMD_SUCCESS;
     note_stream(c, s);
-    jobs.se = end_of(k.st, k.sv);
-    jobs.re = end_of(k.rt, k.rv);
+    if (!k.w) {
+        jobs.se = end_of(k.st, k.sv);
+        jobs.re = end_of(k.rt, k.rv);
+    }
     jobs.force64 = c->typed_force64;
     typed_note tn;
     int64_t most = 0;
     for (int i = 0; i < jobs.n; ++i) {
         const tcp_job &j = jobs.j[i];
         most = std::max(most, j.hi - j.lo);
-        if (j.typed == TCP_SRC_TYPED) note_copy(c, &tn, k.sv, j.src, j.dst + j.lo, (size_t)j.pair);
-        else if (j.typed == TCP_DST_TYPED) note_copy(c, &tn, k.rv, j.dst, j.src + j.lo, (size_t)j.pair);
+        const ddt_view &sv = k.w ? k.w->v[end[i]] : k.sv, &rv = k.w ? k.w->v[end[i]] : k.rv;
+        if (j.typed == TCP_SRC_TYPED) note_copy(c, &tn, sv, j.src, j.dst + j.lo, (size_t)j.pair);
+        else if (j.typed == TCP_DST_TYPED) note_copy(c, &tn, rv, j.dst, j.src + j.lo, (size_t)j.pair);
     }
     int64_t blocks = (most / 16 + kXferThreads * 4 - 1) / (kXferThreads * 4);
     blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, std::max(1, c->max_blocks / jobs.n)));
-    if (c->copy_nt)
+    if (k.w) {  // the same jobs, their datatypes by table end
+        tcpw_jobs wj{};
+        memcpy(wj.j, jobs.j, sizeof(wj.j));
+        memcpy(wj.end, end, (size_t)jobs.n);
+        wj.n = jobs.n;
+        wj.force64 = jobs.force64;
+        wj.tab = k.w->dev;
+        if (c->copy_nt)
+            hipLaunchKernelGGL(typed_copyw_kernel<true>, dim3((unsigned)blocks, (unsigned)jobs.n),
+                               dim3(kXferThreads), 0, s, wj);
+        else
+            hipLaunchKernelGGL(typed_copyw_kernel<false>, dim3((unsigned)blocks, (unsigned)jobs.n),
+                               dim3(kXferThreads), 0, s, wj);
+        if (tn.any && k.w->tab.lds_on) ++c->alltoallw_lds;
+    } else if (c->copy_nt)
         hipLaunchKernelGGL(typed_copy_kernel<true>, dim3((unsigned)blocks, (unsigned)jobs.n),
                            dim3(kXferThreads), 0, s, jobs);
     else
@@ -4922,7 +5079,7 @@ static int alltoall_exchange_typed(ompi_amd_comm_t *c, const a2a_call &k, size_t
                                    char *mine, const ptr_set &peers, size_t slot, int slots,
                                    bool trailing, hipStream_t s) {
     const int n = c->size, me = c->rank;
-    const bool both = k.st && k.rt;
+    const bool both = a2a_st(k, me) && a2a_rt(k, me);  // the own pair's two sides
     auto at = [&](int p) { return (size_t)(slots == 1 ? 0 : p) * slot; };
     auto piece = [&](size_t cnt, int64_t *lo, int64_t *hi) {
         *lo = (int64_t)std::min(cnt, off);
@@ -4930,6 +5087,7 @@ static int alltoall_exchange_typed(ompi_amd_comm_t *c, const a2a_call &k, size_t
     };
     int64_t lo, hi;
     tcp_jobs tj{};
+    uint8_t end[kMaxRanks] = {};
     for (int i = 0; i < n; ++i) {  // my own block, then peers rank+1, rank+2, ...
         const int q = (me + i) % n;
         piece(k.sc[q], &lo, &hi);
@@ -4937,19 +5095,21 @@ static int alltoall_exchange_typed(ompi_amd_comm_t *c, const a2a_call &k, size_t
         const bool direct = i == 0 && !both;
         char *d = direct ? k.rbuf + k.rd[me]
                          : (i == 0 ? mine : const_cast<char *>(peers.p[q])) + at(me) - off;
-        const int typed = k.st ? TCP_SRC_TYPED : (direct && k.rt ? TCP_DST_TYPED : TCP_BYTES);
+        const int typed = a2a_st(k, q) ? TCP_SRC_TYPED : (direct && a2a_rt(k, me) ? TCP_DST_TYPED : TCP_BYTES);
+        end[tj.n] = (uint8_t)(typed == TCP_DST_TYPED ? n + me : q);
         tj.j[tj.n++] = {k.sbuf + k.sd[q], d, lo, hi, (int64_t)k.sc[q], typed};
     }
-    TRY(launch_typed_copy(c, k, tj, s));
+    TRY(launch_typed_copy(c, k, tj, end, s));
     TRY(launch_barrier(c, s));
     tj = tcp_jobs{};
     for (int p = 0; p < n; ++p) {
         piece(k.rc[p], &lo, &hi);
         if (hi == lo || (p == me && !(both && !k.inplace))) continue;
+        end[tj.n] = (uint8_t)(n + p);
         tj.j[tj.n++] = {mine + at(p) - off, k.rbuf + k.rd[p], lo, hi, (int64_t)k.rc[p],
-                        k.rt ? TCP_DST_TYPED : TCP_BYTES};
+                        a2a_rt(k, p) ? TCP_DST_TYPED : TCP_BYTES};
     }
-    TRY(launch_typed_copy(c, k, tj, s));
+    TRY(launch_typed_copy(c, k, tj, end, s));
     return trailing ? launch_barrier(c, s) : OMPI_AMD_SUCCESS;
 }
 
@@ -4960,10 +5120,12 @@ static int alltoall_local_typed(ompi_amd_comm_t *c, const a2a_call &k, hipStream
     if (k.inplace || !k.sc[0]) return OMPI_AMD_SUCCESS;
     const int64_t total = (int64_t)k.sc[0];
     tcp_jobs tj{};
-    if (!(k.st && k.rt)) {
+    const bool st = a2a_st(k, 0), rt = a2a_rt(k, 0);
+    const uint8_t send = 0, recv = 1;  // alltoallw: the two ends of a one-rank table
+    if (!(st && rt)) {
         tj.j[tj.n++] = {k.sbuf + k.sd[0], k.rbuf + k.rd[0], 0, total, total,
-                        k.st ? TCP_SRC_TYPED : TCP_DST_TYPED};
-        return launch_typed_copy(c, k, tj, s);
+                        st ? TCP_SRC_TYPED : rt ? TCP_DST_TYPED : TCP_BYTES};
+        return launch_typed_copy(c, k, tj, st ? &send : &recv, s);
     }
     const stage_half sh = next_half(c);
     const int64_t chunk = (int64_t)(c->scratch_bytes & ~(size_t)255);
@@ -4971,10 +5133,10 @@ static int alltoall_local_typed(ompi_amd_comm_t *c, const a2a_call &k, hipStream
         const int64_t hi = std::min(total, off + chunk);
         tj = tcp_jobs{};
         tj.j[tj.n++] = {k.sbuf + k.sd[0], sh.mine - off, off, hi, total, TCP_SRC_TYPED};
-        TRY(launch_typed_copy(c, k, tj, s));
+        TRY(launch_typed_copy(c, k, tj, &send, s));
         tj = tcp_jobs{};
         tj.j[tj.n++] = {sh.mine - off, k.rbuf + k.rd[0], off, hi, total, TCP_DST_TYPED};
-        TRY(launch_typed_copy(c, k, tj, s));
+        TRY(launch_typed_copy(c, k, tj, &recv, s));
     }
     return OMPI_AMD_SUCCESS;
 }
@@ -5016,25 +5178,34 @@ static int alltoall_fused(ompi_amd_comm_t *c, const a2a_call &k, size_t M, hipSt
     if (a2a_typed(k)) {
         // typed ends: the allgatherv too (its load-once multicast stays a
         // bytes-only optimisation)
-        typed_a2a_args ta{a, end_of(k.st, k.sv), end_of(k.rt, k.rv), c->typed_force64};
-        const bool both = k.st && k.rt;
+        const bool both = a2a_st(k, me) && a2a_rt(k, me);  // the own pair's two sides
         typed_note tn;
         for (int q = 0; q < n; ++q) {
             if (q == me && k.inplace) continue;
             const bool direct = q == me && !both;
             const char *d = direct ? k.rbuf + k.rd[me]
                                    : (q == me ? sh.mine : sh.peers.p[q]) + (size_t)me * (size_t)a.slot;
-            if (k.st) note_copy(c, &tn, k.sv, k.sbuf + k.sd[q], d, k.sc[q]);
-            else if (direct && k.rt) note_copy(c, &tn, k.rv, d, k.sbuf + k.sd[q], k.sc[q]);
+            if (a2a_st(k, q)) note_copy(c, &tn, a2a_sv(k, q), k.sbuf + k.sd[q], d, k.sc[q]);
+            else if (direct && a2a_rt(k, me)) note_copy(c, &tn, a2a_rv(k, me), d, k.sbuf + k.sd[q], k.sc[q]);
         }
-        for (int p = 0; p < n && k.rt; ++p) {
-            if (p == me && !(both && !k.inplace)) continue;
-            note_copy(c, &tn, k.rv, k.rbuf + k.rd[p], sh.mine + (size_t)p * (size_t)a.slot, k.rc[p]);
+        for (int p = 0; p < n; ++p) {
+            if (!a2a_rt(k, p) || (p == me && !(both && !k.inplace))) continue;
+            note_copy(c, &tn, a2a_rv(k, p), k.rbuf + k.rd[p], sh.mine + (size_t)p * (size_t)a.slot, k.rc[p]);
         }
-        if (c->copy_nt)
-            hipLaunchKernelGGL(fused_alltoall_typed_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, ta);
-        else
-            hipLaunchKernelGGL(fused_alltoall_typed_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, ta);
+        if (k.w) {  // one datatype per peer: the ends come from the call's table
+            const a2aw_args wa{a, k.w->dev, c->typed_force64};
+            if (c->copy_nt)
+                hipLaunchKernelGGL(fused_alltoallw_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, wa);
+            else
+                hipLaunchKernelGGL(fused_alltoallw_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, wa);
+            if (k.w->tab.lds_on) ++c->alltoallw_lds;
+        } else {
+            const typed_a2a_args ta{a, end_of(k.st, k.sv), end_of(k.rt, k.rv), c->typed_force64};
+            if (c->copy_nt)
+                hipLaunchKernelGGL(fused_alltoall_typed_kernel<true>, dim3(groups), dim3(kXferThreads), 0, s, ta);
+            else
+                hipLaunchKernelGGL(fused_alltoall_typed_kernel<false>, dim3(groups), dim3(kXferThreads), 0, s, ta);
+        }
         note_launch(c, tn);
     } else if (k.coll == XCH_ALLGATHERV) {  // one block to every peer: load once, store N times
         if (c->copy_nt)
@@ -5118,8 +5289,10 @@ static int alltoall_run(ompi_amd_comm_t *c, const a2a_call &k, size_t M, const p
     const int path = a2a_path(c, pp, M);
     ++(k.coll == XCH_ALLTOALL ? c->alltoall_paths : c->gather_paths)[path];
     if (a2a_typed(k)) ++c->typed_paths[path];
+    if (k.w) ++c->alltoallw_calls;
     if (path == A2A_NONE) return OMPI_AMD_SUCCESS;
     TRY(set_dev(c));
+    if (k.w) TRY(a2aw_upload(c, k.w.get(), s));
     if (path == A2A_LOCAL) {
         if (a2a_typed(k)) return alltoall_local_typed(c, k, s);
         cp_jobs cj{};
@@ -5291,6 +5464,14 @@ static int xch_enter(ompi_amd_comm_t *c, const a2a_call &k, size_t M, bool agree
     TRY(plan_nb_new(c, PEND_ALLTOALL, k.sbuf, k.rbuf, 0, 0, 0, 0, 0, pl));
     (*pl)->a2a = k;
     (*pl)->a2a_M = M;
+    if (k.w) {  // alltoallw: the plan's own table, on the device before any start
+        const int rc = a2aw_own(c, k.w.get());
+        if (rc != OMPI_AMD_SUCCESS) {
+            delete *pl;
+            *pl = nullptr;
+        }
+        return rc;
+    }
     return OMPI_AMD_SUCCESS;
 }
 
@@ -5492,6 +5673,56 @@ static int alltoallv_typed_enter(ompi_amd_comm_t *c, const void *sbuf, const siz
     return xch_enter(c, k, a2a_local_max(c, k), true, f);
 }
 
+// alltoallw: a datatype per peer and side, counts in elements
+// of it, displacements in BYTES (MPI's rule).  In place the receive side
+// describes both directions.  A pair with count 0 keeps neither its datatype
+// nor its displacement.
+static int alltoallw_enter(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts,
+                           const size_t *sdispls, const ompi_amd_ddt_t *const *sddts, void *rbuf,
+                           const size_t *rcounts, const size_t *rdispls,
+                           const ompi_amd_ddt_t *const *rddts, const xch_form &f) {
+    TRY(xch_form_ok(c, f));
+    TRY(a2av_args_ok(c, sbuf, scounts, sdispls, rbuf, rcounts, rdispls));
+    const bool inplace = in_place(sbuf, rbuf);
+    if (!rddts || (!inplace && !sddts)) return OMPI_AMD_ERR_BAD_PARAM;
+    const int n = c->size;
+    auto w = std::make_shared<a2aw_types>();
+    w->v.assign(2 * (size_t)n, ddt_view{});
+    w->on.assign(2 * (size_t)n, 0);
+    size_t sc[kMaxRanks] = {}, sd[kMaxRanks] = {}, rc[kMaxRanks] = {}, rd[kMaxRanks] = {};
+    bool bad = false;
+    // one side of one pair: packed bytes and byte displacement, view and switch
+    auto side = [&](const ompi_amd_ddt_t *ddt, size_t count, size_t displ, int end, size_t *bytes,
+                    size_t *at) {
+        if (!count) return true;
+        size_t size = 1;
+        if (ddt) {
+            // (an empty program would share its LDS position with the next one: a2aw_fill)
+            if (!ddt_view_of(ddt, &w->v[end]) || w->v[end].d.extent < 0 || w->v[end].d.nelem <= 0) return false;
+            w->on[end] = 1;
+            size = (size_t)w->v[end].d.size;
+        }
+        *bytes = mul_or_bad(count, size, &bad);
+        *at = displ;
+        return true;
+    };
+    for (int p = 0; p < n; ++p) {
+        if (!side(rddts[p], rcounts[p], rdispls[p], n + p, &rc[p], &rd[p])) return OMPI_AMD_ERR_BAD_PARAM;
+        if (!inplace && !side(sddts[p], scounts[p], sdispls[p], p, &sc[p], &sd[p]))
+            return OMPI_AMD_ERR_BAD_PARAM;
+        if (inplace) {
+            w->v[p] = w->v[n + p];
+            w->on[p] = w->on[n + p];
+        }
+    }
+    if (bad || (!inplace && sc[c->rank] != rc[c->rank])) return OMPI_AMD_ERR_BAD_PARAM;
+    a2aw_fill(w.get());
+    a2a_call k;
+    a2a_vector(c, sbuf, sc, sd, rbuf, rc, rd, &k);
+    k.w = std::move(w);
+    return xch_enter(c, k, a2a_local_max(c, k), true, f);
+}
+
 static int allgatherv_typed_enter(ompi_amd_comm_t *c, const void *sbuf, size_t scount, void *rbuf,
                                   const size_t *rcounts, const size_t *rdispls,
                                   const ompi_amd_ddt_t *sddt, const ompi_amd_ddt_t *rddt,
@@ -5596,6 +5827,11 @@ XCH_FORMS(scatterv_typed,
           XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
                 void *rbuf, size_t rcount, int root, XCH_T),
           scatter_typed_enter(c, sbuf, 0, scounts, sdispls, rbuf, rcount, root, true, sddt, rddt, f))
+XCH_FORMS(alltoallw,
+          XCH_P(ompi_amd_comm_t *c, const void *sbuf, const size_t *scounts, const size_t *sdispls,
+                const ompi_amd_ddt_t *const *sddts, void *rbuf, const size_t *rcounts,
+                const size_t *rdispls, const ompi_amd_ddt_t *const *rddts),
+          alltoallw_enter(c, sbuf, scounts, sdispls, sddts, rbuf, rcounts, rdispls, rddts, f))
 #undef XCH_T
 #undef XCH_FORMS
 #undef XCH_P

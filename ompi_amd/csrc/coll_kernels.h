@@ -1093,6 +1093,174 @@ __global__ __launch_bounds__(kXferThreads) void fused_alltoall_typed_kernel(type
     }
 }
 
+// ---------------------------------------------------------------- alltoallw
+// One datatype per peer and direction: 2N typed_ends pass the 4 KiB of kernel
+// arguments, so they live in a table in device memory the communicator owns
+// and the kernels take a pointer.  End [q], q < N, is what I send to q; end
+// [N + p] what I receive from p.  The host decides once per table whether the
+// element programs, deduplicated by program pointer, fit the LDS budget
+// (lds_on) and where each one sits there (lds_at, in elements; ends that share
+// a program share the value).  A workgroup then copies the table and the
+// programs into LDS on entry and points every staged end at its LDS copy, so
+// find_elem's search and the bdiv / prefix reads of every granule stay in LDS.
+// The budget is the tile kernels' kDdtLdsElems: 256 elements of 104 B beside
+// the 3.7 KiB table is 30 KiB, five such workgroups per CU of 160 KiB.
+constexpr int kA2awLdsElems = kDdtLdsElems;
+struct a2aw_table {
+    typed_end e[2 * kMaxRanks];
+    int lds_at[2 * kMaxRanks];  // -1: bytes, or not staged
+    int lds_on;                 // every program of the table is staged
+    int pad;
+};
+static_assert(sizeof(a2aw_table) % sizeof(uint64_t) == 0 && sizeof(ddt_elem) % sizeof(uint64_t) == 0,
+              "the staging copies move 8-B words");
+
+__device__ __forceinline__ void lds_words(void *dst, const void *src, int words) {
+    uint64_t *d = static_cast<uint64_t *>(dst);
+    const uint64_t *s = static_cast<const uint64_t *>(src);
+    for (int i = threadIdx.x; i < words; i += kXferThreads) d[i] = s[i];
+}
+
+// ends [0, nend) of *g into *tab, their programs into prog (by the whole workgroup)
+__device__ __forceinline__ void a2aw_stage(const a2aw_table *g, a2aw_table *tab, ddt_elem *prog,
+                                           int nend) {
+    lds_words(tab, g, (int)(sizeof(a2aw_table) / sizeof(uint64_t)));
+    __syncthreads();
+    if (!tab->lds_on) return;
+    for (int i = 0; i < nend; ++i) {
+        const int at = tab->lds_at[i];
+        bool first = at >= 0;
+        for (int j = 0; first && j < i; ++j) first = tab->lds_at[j] != at;
+        if (first)
+            lds_words(prog + at, tab->e[i].d.elems,
+                      tab->e[i].d.nelem * (int)(sizeof(ddt_elem) / sizeof(uint64_t)));
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < nend && tab->lds_at[t] >= 0) tab->e[t].d.elems = prog + tab->lds_at[t];
+    __syncthreads();
+}
+
+struct a2aw_args {
+    a2a_args a;
+    const a2aw_table *tab;
+    int force64;
+};
+static_assert(sizeof(a2aw_args) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// fused_alltoall_typed_kernel with the pair's own datatype on either end:
+// pair (me -> q) walks end [q] in the store, the copy-out of p walks end
+// [N + p], and the own pair goes directly unless both of ITS ends are typed.
+// Each pair picks its granule from its own datatype, base and slot address
+// (coll_typed.h).  The protocol is the typed kernel's, statement for
+// statement.
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void fused_alltoallw_kernel(a2aw_args wa) {
+    __shared__ a2aw_table tab;
+    __shared__ ddt_elem prog[kA2awLdsElems];
+    const a2a_args &a = wa.a;
+    const int t = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+    a2aw_stage(wa.tab, &tab, prog, 2 * a.n);
+    const bool f64 = wa.force64 != 0;
+    const typed_end &own_s = tab.e[a.rank], &own_r = tab.e[a.n + a.rank];
+    const bool both = own_s.d.elems != nullptr && own_r.d.elems != nullptr;
+    int64_t lo, hi;
+    for (int k = 0; k < a.n; ++k) {  // my own block first, then peers rank+1, rank+2, ...
+        const int q = (a.rank + k) % a.n;
+        if (k == 0 && !a.self_copy) continue;
+        a2a_slice(a.scount[q], g, G, &lo, &hi);
+        const typed_end &se = tab.e[q];
+        const bool direct = k == 0 && !both;
+        char *s = const_cast<char *>(a.sbuf) + a.sdispl[q];
+        char *d = direct ? a.rbuf + a.rdispl[q]
+                         : (k == 0 ? a.mine : const_cast<char *>(a.peers.p[q])) + (int64_t)a.rank * a.slot;
+        if (se.d.elems) typed_pipe_copy<false>(se, s, d, lo, hi, a.scount[q], NT && k != 0, f64);
+        else if (direct && own_r.d.elems) typed_pipe_copy<true>(own_r, d, s, lo, hi, a.scount[q], false, f64);
+        else pipe_copy(s, d, lo, hi, NT && k != 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) sys_release();
+    __syncthreads();
+    __shared__ int gave_up;
+    if (t == 0) gave_up = 0;
+    __syncthreads();
+    if (t < a.n && t != a.rank) {
+        __hip_atomic_store(a.peer_flags.p[t] + g * kMaxRanks + a.rank, a.epoch, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        if (!wait_epoch(a.flags + g * kMaxRanks + t, a.epoch, a.err, a.timeout_ticks,
+                        a.flags + kAbortWord))
+            gave_up = 1;
+    }
+    __syncthreads();
+    if (gave_up) return;  // a peer never arrived: its slot holds nothing of this call
+    acquire_once();
+    for (int p = 0; p < a.n; ++p) {
+        if (p == a.rank && !(a.self_copy && both)) continue;
+        a2a_slice(a.rcount[p], g, G, &lo, &hi);
+        const typed_end &re = tab.e[a.n + p];
+        char *s = a.mine + (int64_t)p * a.slot;
+        if (re.d.elems) typed_pipe_copy<true>(re, a.rbuf + a.rdispl[p], s, lo, hi, a.rcount[p], false, f64);
+        else pipe_copy(s, a.rbuf + a.rdispl[p], lo, hi, false);
+    }
+    if (a.mark) {  // the host-observed completion, by the last workgroup
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (t == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            if (__hip_atomic_fetch_add(a.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
+                (uint32_t)G - 1) {
+                __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.mark, a.mark_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
+// typed_copy_kernel whose typed jobs name their datatype by its end in the
+// table: the workgroup stages that one end, and its program when the table's
+// programs are staged (one program never exceeds what all of them fit).
+struct tcpw_jobs {
+    tcp_job j[kMaxRanks];
+    uint8_t end[kMaxRanks];  // a typed job's end in the table
+    int n;
+    int force64;
+    const a2aw_table *tab;
+};
+static_assert(sizeof(tcpw_jobs) <= 4096, "kernel arguments are limited to 4 KiB");
+
+template <bool NT>
+__global__ __launch_bounds__(kXferThreads) void typed_copyw_kernel(tcpw_jobs jobs) {
+    __shared__ typed_end e;
+    __shared__ ddt_elem prog[kA2awLdsElems];
+    acquire_once();
+    const tcp_job jb = jobs.j[blockIdx.y];
+    if (jb.typed != TCP_BYTES) {
+        static_assert(sizeof(typed_end) % sizeof(uint64_t) == 0, "staged as 8-B words");
+        lds_words(&e, &jobs.tab->e[jobs.end[blockIdx.y]], (int)(sizeof(typed_end) / sizeof(uint64_t)));
+        __syncthreads();
+        if (jobs.tab->lds_on) {
+            lds_words(prog, e.d.elems, e.d.nelem * (int)(sizeof(ddt_elem) / sizeof(uint64_t)));
+            __syncthreads();
+            if (threadIdx.x == 0) e.d.elems = prog;
+            __syncthreads();
+        }
+    }
+    int64_t lo, hi;
+    a2a_slice(jb.hi - jb.lo, (int)blockIdx.x, (int)gridDim.x, &lo, &hi);
+    lo += jb.lo;
+    hi += jb.lo;
+    if (jb.typed == TCP_SRC_TYPED)
+        typed_pipe_copy<false>(e, const_cast<char *>(jb.src), jb.dst, lo, hi, jb.pair, NT,
+                               jobs.force64 != 0);
+    else if (jb.typed == TCP_DST_TYPED)
+        typed_pipe_copy<true>(e, jb.dst, const_cast<char *>(jb.src), lo, hi, jb.pair, false,
+                              jobs.force64 != 0);
+    else
+        pipe_copy(jb.src, jb.dst, lo, hi, NT);
+    xfer_epilogue();
+}
+
 // ---------------------------------------------------------------- launch rows
 using red_launch_fn = hipError_t (*)(dim3, const ptr_set &, const ptr_set &, int, int, int, int,
                                      const red_jobs &, hipStream_t);

@@ -274,6 +274,23 @@ ROCM_DECLARE_FORMS(scatterv, ROCM_SCATTERV_PARAMS)
 #error "ROCM_HAVE_TYPED_XCH needs the alltoall and the gather slots"
 #endif
 
+/* MPI_Alltoallw, blocking, nonblocking and persistent: one device program per
+ * peer (ompi_amd_alltoallw), so with ROCM_HAVE_TYPED_XCH only.
+ * The harnesses' stand-in coll.h files have no such slots: a harness build
+ * leaves this part out. */
+#if defined(ROCM_HAVE_TYPED_XCH) && !defined(HARNESS_COLL)
+#define ROCM_HAVE_ALLTOALLW 1
+#define ROCM_ALLTOALLW_PARAMS                                                                  \
+    const void *sbuf, const int *scounts, const int *sdisps, struct ompi_datatype_t *const *sdtypes, \
+        void *rbuf, const int *rcounts, const int *rdisps, struct ompi_datatype_t *const *rdtypes,   \
+        struct ompi_communicator_t *comm
+int mca_coll_rocm_alltoallw(ROCM_ALLTOALLW_PARAMS, mca_coll_base_module_t *module);
+int mca_coll_rocm_ialltoallw(ROCM_ALLTOALLW_PARAMS, ompi_request_t **request,
+                             mca_coll_base_module_t *module);
+int mca_coll_rocm_alltoallw_init(ROCM_ALLTOALLW_PARAMS, struct ompi_info_t *info,
+                                 ompi_request_t **request, mca_coll_base_module_t *module);
+#endif
+
 END_C_DECLS
 
 #endif /* MCA_COLL_ROCM_EXPORT_H */

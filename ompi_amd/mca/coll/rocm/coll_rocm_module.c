@@ -306,6 +306,12 @@ static void rocm_module_destruct(mca_coll_rocm_module_t *m)
     if (NULL != m->c_coll.coll_alltoallv_init_module)
         OBJ_RELEASE(m->c_coll.coll_alltoallv_init_module);
 #endif
+#ifdef ROCM_HAVE_ALLTOALLW
+    if (NULL != m->c_coll.coll_alltoallw_module) OBJ_RELEASE(m->c_coll.coll_alltoallw_module);
+    if (NULL != m->c_coll.coll_ialltoallw_module) OBJ_RELEASE(m->c_coll.coll_ialltoallw_module);
+    if (NULL != m->c_coll.coll_alltoallw_init_module)
+        OBJ_RELEASE(m->c_coll.coll_alltoallw_init_module);
+#endif
 #ifdef ROCM_HAVE_GATHER
 #define DROP(fn) if (NULL != m->c_coll.coll_##fn##_module) OBJ_RELEASE(m->c_coll.coll_##fn##_module);
     ROCM_GATHER_SLOTS(DROP)
@@ -371,6 +377,11 @@ mca_coll_base_module_t *mca_coll_rocm_comm_query(struct ompi_communicator_t *com
     m->super.coll_alltoall_init = mca_coll_rocm_alltoall_init;
     m->super.coll_alltoallv_init = mca_coll_rocm_alltoallv_init;
 #endif
+#ifdef ROCM_HAVE_ALLTOALLW
+    m->super.coll_alltoallw = mca_coll_rocm_alltoallw;
+    m->super.coll_ialltoallw = mca_coll_rocm_ialltoallw;
+    m->super.coll_alltoallw_init = mca_coll_rocm_alltoallw_init;
+#endif
 #ifdef ROCM_HAVE_GATHER
 #define OFFER(fn) m->super.coll_##fn = mca_coll_rocm_##fn;
     ROCM_GATHER_SLOTS(OFFER)
@@ -423,6 +434,11 @@ int mca_coll_rocm_module_enable(mca_coll_base_module_t *module, struct ompi_comm
     SAVE(ialltoallv);
     SAVE(alltoall_init);
     SAVE(alltoallv_init);
+#endif
+#ifdef ROCM_HAVE_ALLTOALLW
+    SAVE(alltoallw);
+    SAVE(ialltoallw);
+    SAVE(alltoallw_init);
 #endif
 #ifdef ROCM_HAVE_GATHER
 #define SAVE_ONE(fn) SAVE(fn);
@@ -2060,6 +2076,138 @@ int mca_coll_rocm_alltoallv_init(const void *sbuf, const int *scounts, const int
     return rocm_alltoallv_common(sbuf, scounts, sdisps, sdtype, rbuf, rcounts, rdisps, rdtype, comm,
                                  info, request, (mca_coll_rocm_module_t *) module, A2A_PERSISTENT);
 }
+
+#ifdef ROCM_HAVE_ALLTOALLW
+/* ---------------------------------------------------------------- alltoallw
+ * MPI_Alltoallw and its nonblocking and persistent forms: a datatype per peer
+ * on either side, displacements in bytes.  A peer whose block is contiguous
+ * goes to ompi_amd_alltoallw as bytes, any other with opal_rocm_device_ddt's
+ * program (how == 3 per peer: nothing is packed).  A datatype that moves data
+ * and has neither is this rank's knowledge alone, so the ranks agree on it
+ * first and the whole call goes to the saved function if any rank has one.
+ * After that the vote, the lock and the staging are the other exchange slots',
+ * with each buffer as one operand of bytes: the span its blocks touch, which
+ * a host rank copies to the device and back as it is. */
+static int a2aw_side(const int *counts, const int *disps, struct ompi_datatype_t *const *types, int n,
+                     size_t *c, size_t *d, const ompi_amd_ddt_t **ddt, ptrdiff_t *lo, ptrdiff_t *hi)
+{
+    int ok = 1;
+    *lo = *hi = 0;
+    for (int p = 0; p < n; ++p) {
+        ptrdiff_t lb, ext, tlb, text, reach;
+        size_t size = 0;
+        c[p] = d[p] = 0;
+        ddt[p] = NULL;
+        if (counts[p] <= 0) continue;
+        (void) ompi_datatype_type_size(types[p], &size);
+        if (0 == size) continue;
+        (void) ompi_datatype_get_extent(types[p], &lb, &ext);
+        (void) ompi_datatype_get_true_extent(types[p], &tlb, &text);
+        reach = (ptrdiff_t) (counts[p] - 1) * ext;
+        if (disps[p] + tlb + (reach < 0 ? reach : 0) < *lo) *lo = disps[p] + tlb + (reach < 0 ? reach : 0);
+        if (disps[p] + tlb + text + (reach > 0 ? reach : 0) > *hi)
+            *hi = disps[p] + tlb + text + (reach > 0 ? reach : 0);
+        if (disps[p] + tlb >= 0 && ompi_datatype_is_contiguous_memory_layout(types[p], counts[p])) {
+            c[p] = (size_t) counts[p] * size;
+            d[p] = (size_t) (disps[p] + tlb);
+        } else if (disps[p] >= 0 && NULL != (ddt[p] = opal_rocm_device_ddt(
+                                                 (const struct opal_datatype_t *) types[p]))) {
+            c[p] = (size_t) counts[p];
+            d[p] = (size_t) disps[p];
+        } else {
+            ok = 0;
+        }
+    }
+    return ok;
+}
+
+static int rocm_alltoallw_common(ROCM_ALLTOALLW_PARAMS, struct ompi_info_t *info,
+                                 ompi_request_t **request, mca_coll_rocm_module_t *m, int form)
+{
+    const int inplace = MPI_IN_PLACE == sbuf;
+    const int n = ompi_comm_size(comm);
+    size_t sc[OMPI_AMD_MAX_RANKS], sd[OMPI_AMD_MAX_RANKS], rc_[OMPI_AMD_MAX_RANKS],
+        rd[OMPI_AMD_MAX_RANKS];
+    const ompi_amd_ddt_t *st[OMPI_AMD_MAX_RANKS], *rt[OMPI_AMD_MAX_RANKS];
+    ptrdiff_t slo = 0, shi = 0, rlo = 0, rhi = 0;
+    int typable = a2aw_side(rcounts, rdisps, rdtypes, n, rc_, rd, rt, &rlo, &rhi);
+    struct rocm_nb_stage *stage = NULL;
+    ompi_amd_request_t *nb = NULL;
+    ompi_amd_plan_t *plan = NULL;
+    ompi_request_t *inner = NULL;
+    const void *sb;
+    void *rb;
+    int path, rc, ok;
+    if (!inplace) typable = a2aw_side(scounts, sdisps, sdtypes, n, sc, sd, st, &slo, &shi) && typable;
+    {
+        /* the bytes each buffer's blocks touch, from the lowest one on */
+        rocm_operand_t o[2] = {{inplace || shi == slo ? (void *) sbuf : (char *) sbuf + slo,
+                                (size_t) (shi - slo), MPI_BYTE, 1, 0},
+                               {rhi == rlo ? rbuf : (char *) rbuf + rlo, (size_t) (rhi - rlo), MPI_BYTE,
+                                1, 1}};
+        ok = (rhi == rlo || dev(rbuf)) && (inplace || shi == slo || dev(sbuf));
+        rc = rocm_a2a_begin(m, form, take_device_path(m, typable), ok, o, &stage, &path);
+        if (OMPI_SUCCESS != rc) return rc;
+        sb = inplace || shi == slo ? sbuf : (const void *) ((char *) o[0].use - slo);
+        rb = rhi == rlo ? rbuf : (void *) ((char *) o[1].use - rlo);
+        if (ROCM_DEVICE != path) {
+            if (A2A_BLOCKING == form) {
+                rc = m->c_coll.coll_alltoallw(sb, scounts, sdisps, sdtypes, rb, rcounts, rdisps, rdtypes,
+                                              comm, m->c_coll.coll_alltoallw_module);
+                return rocm_unstage(m, o, 2, rc);
+            }
+            rc = A2A_NONBLOCKING == form
+                     ? m->c_coll.coll_ialltoallw(sb, scounts, sdisps, sdtypes, rb, rcounts, rdisps,
+                                                 rdtypes, comm, &inner,
+                                                 m->c_coll.coll_ialltoallw_module)
+                     : m->c_coll.coll_alltoallw_init(sb, scounts, sdisps, sdtypes, rb, rcounts, rdisps,
+                                                     rdtypes, comm, info, &inner,
+                                                     m->c_coll.coll_alltoallw_init_module);
+            return rocm_saved_post(rc, inner, stage, comm, request);
+        }
+        for (int p = 0; p < n; ++p) {
+            if (NULL != rt[p] || (!inplace && NULL != st[p])) {
+                m->typed_calls++;
+                break;
+            }
+        }
+        if (inplace) sb = (const void *) 1;
+        if (A2A_BLOCKING == form) {
+            rc = ompi_amd_alltoallw(m->dev_comm, sb, inplace ? NULL : sc, inplace ? NULL : sd,
+                                    inplace ? NULL : st, rb, rc_, rd, rt, NULL);
+            return rocm_dev_finish(m, o, 2, rc);
+        }
+    }
+    if (A2A_NONBLOCKING == form) {
+        rc = ompi_amd_ialltoallw(m->dev_comm, sb, inplace ? NULL : sc, inplace ? NULL : sd,
+                                 inplace ? NULL : st, rb, rc_, rd, rt, NULL, &nb);
+        return rocm_nb_post(rc, nb, stage, comm, request);
+    }
+    rc = ompi_amd_alltoallw_init(m->dev_comm, sb, inplace ? NULL : sc, inplace ? NULL : sd,
+                                 inplace ? NULL : st, rb, rc_, rd, rt, &plan);
+    return rocm_wrap_plan(rc, plan, stage, comm, request);
+}
+
+int mca_coll_rocm_alltoallw(ROCM_ALLTOALLW_PARAMS, mca_coll_base_module_t *module)
+{
+    return rocm_alltoallw_common(sbuf, scounts, sdisps, sdtypes, rbuf, rcounts, rdisps, rdtypes, comm,
+                                 NULL, NULL, (mca_coll_rocm_module_t *) module, A2A_BLOCKING);
+}
+
+int mca_coll_rocm_ialltoallw(ROCM_ALLTOALLW_PARAMS, ompi_request_t **request,
+                             mca_coll_base_module_t *module)
+{
+    return rocm_alltoallw_common(sbuf, scounts, sdisps, sdtypes, rbuf, rcounts, rdisps, rdtypes, comm,
+                                 NULL, request, (mca_coll_rocm_module_t *) module, A2A_NONBLOCKING);
+}
+
+int mca_coll_rocm_alltoallw_init(ROCM_ALLTOALLW_PARAMS, struct ompi_info_t *info,
+                                 ompi_request_t **request, mca_coll_base_module_t *module)
+{
+    return rocm_alltoallw_common(sbuf, scounts, sdisps, sdtypes, rbuf, rcounts, rdisps, rdtypes, comm,
+                                 info, request, (mca_coll_rocm_module_t *) module, A2A_PERSISTENT);
+}
+#endif /* ROCM_HAVE_ALLTOALLW */
 #endif /* ROCM_HAVE_ALLTOALL */
 
 #ifdef ROCM_HAVE_GATHER
