@@ -38,9 +38,21 @@
  * completes when its data is in its buffer.  Host-side waits (a full
  * 64-slot ring, wait, probe) are bounded by param "p2p_timeout_ms" (-1: the
  * communicator's timeout_ms, the default; 0: no limit — the PML glue's
- * setting, MPI semantics).  The byte count is the message size; the MCA
- * glue packs non-contiguous datatypes first.
-  */
+ * setting, MPI semantics).  The byte count is the message size.
+ *
+ * Derived datatypes.  The *_typed forms take a count of elements of an
+ * ompi_amd_ddt_t (NULL: bytes) based at a device buffer, and the kernel that
+ * moves the message walks the datatype: the sender packs straight into the
+ * eager cell (at most 4 KiB packed) or a send stage, the receiver's copy-out
+ * scatters into the receive layout.  On the wire a message
+ * is its packed stream, so `bytes` in a status or a probe is packed bytes,
+ * matching is unchanged, and a typed call on one side meets a byte call, or
+ * a different datatype of the same packed length, on the other.  There is no
+ * typed rendezvous: with "p2p_user_ipc" = 1, or when the pool has no stage
+ * left, a typed send returns OMPI_AMD_ERR_UNSUPPORTED before it took
+ * anything, and the MCA glue packs non-contiguous datatypes first as it
+ * does for host buffers.
+ */
 #ifndef OMPI_AMD_P2P_H
 #define OMPI_AMD_P2P_H
 
@@ -94,6 +106,34 @@ int ompi_amd_recv(ompi_amd_comm_t *comm, void *buf, size_t bytes, int src, int t
 int ompi_amd_sendrecv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, int dst, int stag,
                       void *rbuf, size_t rbytes, int src, int rtag, void *stream,
                       ompi_amd_status_t *status);
+/* The same calls for `count` elements of `ddt` based at the device buffer
+ * `buf` (ddt NULL: count bytes).  `ddt` is kept by reference until the
+ * request completes.  A message shorter than the receive writes exactly its
+ * bytes of the stream (it may end inside an element) and nothing else; bytes
+ * the datatype does not own are never written.  OMPI_AMD_ERR_BAD_PARAM, with
+ * no request, for what the byte forms refuse, a host buffer, a datatype
+ * without a device program or with a negative extent, and count * size past
+ * SIZE_MAX.  Counters (get_param): p2p_typed_eager, p2p_typed_staged (sends
+ * by path), p2p_typed_recv (receives whose copy-out walked a datatype),
+ * p2p_typed_lds (those with the program in LDS), p2p_typed_granule (access
+ * width of the last typed launch), p2p_typed_walk64 (typed launches that ran
+ * the 64-bit walk; "typed_force64" forces it).  A typed staged send does not
+ * count in p2p_staged_sends.  sendrecv_typed posts its receive only once its
+ * send can no longer be refused: after OMPI_AMD_ERR_UNSUPPORTED it has
+ * matched no message. */
+int ompi_amd_isend_typed(ompi_amd_comm_t *comm, const void *buf, size_t count,
+                         const ompi_amd_ddt_t *ddt, int dst, int tag, int mode, void *stream,
+                         ompi_amd_p2p_request_t **request);
+int ompi_amd_irecv_typed(ompi_amd_comm_t *comm, void *buf, size_t count, const ompi_amd_ddt_t *ddt,
+                         int src, int tag, void *stream, ompi_amd_p2p_request_t **request);
+int ompi_amd_send_typed(ompi_amd_comm_t *comm, const void *buf, size_t count,
+                        const ompi_amd_ddt_t *ddt, int dst, int tag, int mode, void *stream);
+int ompi_amd_recv_typed(ompi_amd_comm_t *comm, void *buf, size_t count, const ompi_amd_ddt_t *ddt,
+                        int src, int tag, void *stream, ompi_amd_status_t *status);
+int ompi_amd_sendrecv_typed(ompi_amd_comm_t *comm, const void *sbuf, size_t scount,
+                            const ompi_amd_ddt_t *sddt, int dst, int stag, void *rbuf, size_t rcount,
+                            const ompi_amd_ddt_t *rddt, int src, int rtag, void *stream,
+                            ompi_amd_status_t *status);
 /* *done = 1 when complete (status filled for receives; status may be NULL).
  * Every test / wait also matches pending receives of the communicator. */
 int ompi_amd_p2p_test(ompi_amd_p2p_request_t *request, int *done, ompi_amd_status_t *status);

@@ -298,6 +298,21 @@ PROTOTYPES = [
     ("ompi_amd_sendrecv", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.c_void_p, _C.c_size_t,
       _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(Status)]),
+    # the same with (count, datatype handle) in place of bytes
+    ("ompi_amd_isend_typed", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,
+      _C.POINTER(_C.c_void_p)]),
+    ("ompi_amd_irecv_typed", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_int, _C.c_int, _C.c_void_p,
+      _C.POINTER(_C.c_void_p)]),
+    ("ompi_amd_send_typed", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p]),
+    ("ompi_amd_recv_typed", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_int, _C.c_int, _C.c_void_p,
+      _C.POINTER(Status)]),
+    ("ompi_amd_sendrecv_typed", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_int, _C.c_int, _C.c_void_p, _C.c_size_t,
+      _C.c_void_p, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(Status)]),
     ("ompi_amd_p2p_test", _C.c_int, [_C.c_void_p, _C.POINTER(_C.c_int), _C.POINTER(Status)]),
     ("ompi_amd_p2p_wait", _C.c_int, [_C.c_void_p, _C.POINTER(Status)]),
     ("ompi_amd_p2p_free", _C.c_int, [_C.c_void_p]),

@@ -4906,18 +4906,6 @@ static bool a2a_rt(const a2a_call &k, int p) { return k.w ? k.w->on[k.w->on.size
 static const ddt_view &a2a_sv(const a2a_call &k, int q) { return k.w ? k.w->v[q] : k.sv; }
 static const ddt_view &a2a_rv(const a2a_call &k, int p) { return k.w ? k.w->v[k.w->v.size() / 2 + p] : k.rv; }
 
-static typed_end end_of(bool on, const ddt_view &v) {
-    typed_end e{};
-    if (!on) return e;
-    e.d = v.d;
-    e.gran = v.gran;
-    for (int lg = 0; lg < 5; ++lg) {
-        const int64_t sg = v.d.size >> lg;
-        if ((v.d.size & ((1 << lg) - 1)) == 0 && sg < (1ll << 32)) e.sdiv[lg] = make_fdiv((uint32_t)sg);
-    }
-    return e;
-}
-
 // What the copies of one typed launch pick (coll_typed.h's rule, which the
 // kernel evaluates again per copy): the smallest granule, any 64-bit walk.
 struct typed_note {
@@ -6349,6 +6337,8 @@ int comm_barrier(ompi_amd_comm_t *c, hipStream_t s) {
 }
 
 int comm_sticky(ompi_amd_comm_t *c) { return check_sticky(c); }
+
+bool comm_typed_force64(const ompi_amd_comm_t *c) { return c->typed_force64 != 0; }
 
 hipStream_t comm_call_stream(ompi_amd_comm_t *c, void *stream) { return comm_stream(c, stream); }
 

@@ -908,6 +908,19 @@ struct typed_end {
     int gran;
 };
 
+// The end of a view (host side; on false: bytes).
+inline typed_end end_of(bool on, const ddt_view &v) {
+    typed_end e{};
+    if (!on) return e;
+    e.d = v.d;
+    e.gran = v.gran;
+    for (int lg = 0; lg < 5; ++lg) {
+        const int64_t sg = v.d.size >> lg;
+        if ((v.d.size & ((1 << lg) - 1)) == 0 && sg < (1ll << 32)) e.sdiv[lg] = make_fdiv((uint32_t)sg);
+    }
+    return e;
+}
+
 // ng G-byte granules from stream byte lo on: `typed` is the typed base of the
 // block, `contig` the address of stream byte lo.  kDdtUnroll typed addresses
 // first, then as many independent loads in flight, then the stores

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "../../include/ompi_amd_coll.h"
+#include "../../include/ompi_amd_ddt.h"
 
 namespace ompi_amd {
 
@@ -115,6 +116,33 @@ struct xfer_sig {
     uint32_t *done = nullptr;
 };
 int xfer_copy_sig(const void *src, void *dst, size_t bytes, hipStream_t s, const xfer_sig &sig);
+// The persistent copy grids' cap: one workgroup per CU, or OMPI_AMD_OSC_MAX_BLOCKS.
+int64_t osc_grid_cap();
+// p2p_typed.hip: the same four copies with a derived datatype on the caller's
+// end (`typed`: the buffer the datatype is based at) and the packed stream on
+// the library's.  p2p_type_of: the packed bytes per element;
+// false for a datatype that is no device program or has a negative extent.
+// force64: param "typed_force64".  *pick: what the launch chose.
+// xfer_unpack_sig uses sig's wait, wait_v, err and ticks only: its stores are
+// local and the kernel boundary completes it (the caller records an event).
+struct typed_pick {
+    int granule = 0;   // access width in bytes (coll_typed.h's typed_granule)
+    bool lds = false;  // the element program was staged in LDS
+    bool w64 = false;  // the 64-bit walk ran (coll_typed.h's typed_walk64)
+};
+bool p2p_type_of(const ompi_amd_ddt_t *ddt, size_t *size);
+int eager_put_typed(const ompi_amd_ddt_t *ddt, const void *typed, char *cell, size_t bytes, bool force64,
+                    uint64_t *flag, uint64_t v, uint64_t *mark, uint64_t mark_v, hipStream_t s,
+                    typed_pick *pick);
+int eager_get_typed(const ompi_amd_ddt_t *ddt, const char *cell, void *typed, size_t bytes, bool force64,
+                    const uint64_t *flag, uint64_t v, int *err, uint64_t ticks, uint64_t *mark,
+                    uint64_t mark_v, hipStream_t s, typed_pick *pick);
+int xfer_pack_sig(const ompi_amd_ddt_t *ddt, const void *typed, void *stage, size_t bytes, bool force64,
+                  hipStream_t s, const xfer_sig &sig, typed_pick *pick);
+int xfer_unpack_sig(const ompi_amd_ddt_t *ddt, const void *stage, void *typed, size_t bytes, bool force64,
+                    hipStream_t s, const xfer_sig &sig, typed_pick *pick);
+// param "typed_force64" of c
+bool comm_typed_force64(const ompi_amd_comm_t *c);
 // Point-to-point mailboxes of the communicator (created with it).
 p2p_state *comm_p2p(ompi_amd_comm_t *c);
 // The one-sided part's per-communicator state (NULL until it sets one).

@@ -1059,7 +1059,7 @@ static int target_ptr(ompi_amd_win_t *w, int target, size_t disp, size_t bytes, 
 }
 
 
-static int64_t osc_grid_cap() {
+int64_t osc_grid_cap() {
     static const int64_t cap = [] {
         const char *e = getenv("OMPI_AMD_OSC_MAX_BLOCKS");
         return (e && atoll(e) > 0) ? atoll(e) : (int64_t)kOscMaxBlocks;

@@ -64,6 +64,13 @@
 //            the copy kernel cannot read pageable memory); a staged message
 //            received into host memory lands in a device receive stage first
 //            and is copied out before it completes.
+//   typed    the *_typed forms: the same wire format — a
+//            message is its packed stream — with the datatype walked by the
+//            kernel that moves it (p2p_typed.hip).  The sender packs straight
+//            into the slot's eager cell or a send stage and signals as above
+//            (no typed rendezvous: UNSUPPORTED instead); the receiver's
+//            copy-out scatters from whatever device source the message names,
+//            or from a receive stage for a host source.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -140,6 +147,10 @@ struct p2p_state {
     struct inflight { int dst; uint64_t seq; stage st; };
     std::deque<inflight> staged;  // sends whose stage the receiver may still read
     int64_t staged_sends = 0, direct_sends = 0, host_sends = 0, host_recvs = 0;
+    // typed sends through a cell / a stage, receives whose copy-out walked a
+    // datatype, those of them with the program in LDS, the last launch's width
+    int64_t typed_eager = 0, typed_staged = 0, typed_recv = 0, typed_lds = 0, typed_granule = 0;
+    int64_t typed_walk64 = 0;  // typed launches, either side, that ran the 64-bit walk
     int rank = 0, size = 0;
     char name[256] = {0};
     pair_q *q = nullptr;
@@ -248,6 +259,7 @@ struct ompi_amd_p2p_request {
     void *pinned2 = nullptr;   // inl 4: the sender's eager area (the stage's flag)
     ompi_amd_status_t st{};
     void *host_dst = nullptr;  // a host receive buffer: the copy lands in `rstage` first
+    const ompi_amd_ddt_t *ddt = nullptr;  // a typed receive: the copy-out walks it from `buf`
     stage rstage{};
     bool has_rstage = false;
 };
@@ -291,6 +303,12 @@ int p2p_get_param(p2p_state *p, const char *key, int64_t *v) {
     else if (!strcmp(key, "p2p_host_recvs")) *v = p->host_recvs;
     else if (!strcmp(key, "p2p_host_stage_sends")) *v = p->host_stage_sends;
     else if (!strcmp(key, "p2p_unsafe_sends")) *v = p->unsafe_sends;
+    else if (!strcmp(key, "p2p_typed_eager")) *v = p->typed_eager;
+    else if (!strcmp(key, "p2p_typed_staged")) *v = p->typed_staged;
+    else if (!strcmp(key, "p2p_typed_recv")) *v = p->typed_recv;
+    else if (!strcmp(key, "p2p_typed_lds")) *v = p->typed_lds;
+    else if (!strcmp(key, "p2p_typed_granule")) *v = p->typed_granule;
+    else if (!strcmp(key, "p2p_typed_walk64")) *v = p->typed_walk64;
     else return OMPI_AMD_ERR_UNSUPPORTED;
     return OMPI_AMD_SUCCESS;
 }
@@ -581,6 +599,22 @@ static bool p2p_trace() {
     return on;
 }
 
+static void count_typed_recv(p2p_state *p, const typed_pick &pick) {
+    ++p->typed_recv;
+    p->typed_lds += pick.lds ? 1 : 0;
+    p->typed_granule = pick.granule;
+    p->typed_walk64 += pick.w64 ? 1 : 0;
+}
+
+// The typed copy-out of `n` stream bytes at device address `from` into r's
+// datatype (sg: the flag to wait for, if any); completes by r's event.
+static int unpack_recv(p2p_state *p, ompi_amd_p2p_request *r, const char *from, size_t n, const xfer_sig &sg) {
+    typed_pick pick;
+    const int rc = xfer_unpack_sig(r->ddt, from, r->buf, n, comm_typed_force64(p->c), r->stream, sg, &pick);
+    count_typed_recv(p, pick);
+    return rc;
+}
+
 // Claim `m` for receive `r` and launch its copy.
 static void start_recv(p2p_state *p, ompi_amd_p2p_request *r, msg_slot *m, int s) {
     if (p2p_trace())
@@ -615,8 +649,19 @@ static void start_recv(p2p_state *p, ompi_amd_p2p_request *r, msg_slot *m, int s
             memcpy(r->host_dst, from, n);
             return;
         }
-        rc = record_hip(hipMemcpyAsync(r->buf, from, n, hipMemcpyHostToDevice, r->stream),
-                        "hipMemcpyAsync (p2p host-stage receive)");
+        char *to = static_cast<char *>(r->buf);
+        if (r->ddt) {  // lands in a device stage, unpacked from there
+            if (take_stage(p, p->recv_free, n, false, &r->rstage)) {
+                r->has_rstage = true;
+                to = r->rstage.buf;
+            } else {
+                rc = record_hip(hipErrorOutOfMemory, "p2p receive stage");
+            }
+        }
+        if (rc == OMPI_AMD_SUCCESS)
+            rc = record_hip(hipMemcpyAsync(to, from, n, hipMemcpyHostToDevice, r->stream),
+                            "hipMemcpyAsync (p2p host-stage receive)");
+        if (rc == OMPI_AMD_SUCCESS && r->ddt) rc = unpack_recv(p, r, to, n, xfer_sig{});
         if (rc == OMPI_AMD_SUCCESS) rc = record_copy(p, r);
         if (rc != OMPI_AMD_SUCCESS) r->rc = r->st.error = rc;
         return;
@@ -641,11 +686,20 @@ static void start_recv(p2p_state *p, ompi_amd_p2p_request *r, msg_slot *m, int s
             const int64_t ms = comm_timeout_ms(p->c);
             const uint64_t ticks = ms > 0 ? (uint64_t)ms * 100000ull : (1ull << 62);  // 100 MHz
             if (!r->host_dst) take_mark(r);  // a host receive's copy out still needs the event
-            rc = eager_get(src, dst, n, reinterpret_cast<const uint64_t *>(src + kEager), m->seq + 1,
-                           comm_err_dev(p->c), ticks, r->mark, r->mark_v, r->stream);
+            if (r->ddt) {
+                typed_pick pick;
+                rc = eager_get_typed(r->ddt, src, dst, n, comm_typed_force64(p->c),
+                                     reinterpret_cast<const uint64_t *>(src + kEager), m->seq + 1,
+                                     comm_err_dev(p->c), ticks, r->mark, r->mark_v, r->stream, &pick);
+                count_typed_recv(p, pick);
+            } else {
+                rc = eager_get(src, dst, n, reinterpret_cast<const uint64_t *>(src + kEager), m->seq + 1,
+                               comm_err_dev(p->c), ticks, r->mark, r->mark_v, r->stream);
+            }
         } else if (m->inl == 4) {  // a signalled stage: the copy waits for the sender's flag
             const char *fc = nullptr;
-            rc = comm_import(p->c, s, m->fd, &fc, true, &r->pinned2);
+            if (s == p->rank) fc = p->eager + (m->fd.off - p->eager_d.off);  // a typed send to self
+            else rc = comm_import(p->c, s, m->fd, &fc, true, &r->pinned2);
             if (rc == OMPI_AMD_SUCCESS) rc = eager_area(p);  // this rank's copy counters
             if (rc == OMPI_AMD_SUCCESS) {
                 const int64_t ms = comm_timeout_ms(p->c);
@@ -654,12 +708,18 @@ static void start_recv(p2p_state *p, ompi_amd_p2p_request *r, msg_slot *m, int s
                 sg.wait_v = m->seq + 1;
                 sg.err = comm_err_dev(p->c);
                 sg.ticks = ms > 0 ? (uint64_t)ms * 100000ull : (1ull << 62);
-                if (!r->host_dst) take_mark(r);
-                sg.mark = r->mark;
-                sg.mark_v = r->mark_v;
-                sg.done = p->recv_done(s, m->seq);
-                rc = xfer_copy_sig(src, dst, n, r->stream, sg);
+                if (r->ddt) {
+                    rc = unpack_recv(p, r, src, n, sg);
+                } else {
+                    if (!r->host_dst) take_mark(r);
+                    sg.mark = r->mark;
+                    sg.mark_v = r->mark_v;
+                    sg.done = p->recv_done(s, m->seq);
+                    rc = xfer_copy_sig(src, dst, n, r->stream, sg);
+                }
             }
+        } else if (r->ddt) {
+            rc = unpack_recv(p, r, src, n, xfer_sig{});
         } else {
             rc = xfer_copy(src, dst, n, r->stream, nullptr, false);  // dst: this GPU's memory
         }
@@ -825,6 +885,100 @@ static void fill_status(const ompi_amd_p2p_request *r, ompi_amd_status_t *st) {
     }
 }
 
+// The ring slot of a send's next message must be free: its previous message
+// completed (DONE) or it was never used; wait for the receiver otherwise
+// (false once p2p_timeout_ms has passed).  Under p->mu.
+static bool slot_free(p2p_state *p, msg_slot &m, int dst) {
+    const double t0 = now_s();
+    for (;;) {
+        const uint32_t st = m.state.load(std::memory_order_acquire);
+        if (st == S_FREE || st == S_DONE) return true;
+        progress(p);  // our own receives keep flowing meanwhile
+        sched_yield();
+        if (over(p, t0)) {
+            record_msg("p2p send to %d: %d messages unmatched for %.1f s", dst, kSlots, limit_s(p));
+            return false;
+        }
+    }
+}
+
+// Fill the slot and publish it.  Under p->mu.
+static void post(p2p_state *p, pair_q &q, msg_slot &m, int dst, uint64_t seq, int tag, size_t bytes,
+                 uint64_t raw, const ipc_desc &d, const ipc_desc &fd, uint32_t inl) {
+    m.tag = tag;
+    m.seq = seq;
+    m.bytes = bytes;
+    m.raw = raw;
+    m.d = d;
+    m.fd = fd;
+    m.inl = inl;
+    if (p2p_trace())
+        fprintf(stderr, "[p2p %d] post -> dst %d seq %llu tag %d bytes %zu inl %u\n", p->rank, dst,
+                (unsigned long long)seq, tag, bytes, m.inl);
+    m.state.store(S_POSTED, std::memory_order_release);
+    q.posted.store(seq + 1, std::memory_order_release);
+}
+
+static int post_recv(ompi_amd_comm_t *c, void *buf, size_t bytes, const ompi_amd_ddt_t *ddt, int src, int tag,
+                     void *stream, ompi_amd_p2p_request_t **out) {
+    if (!c || !out || (bytes && !buf) || tag < OMPI_AMD_ANY_TAG) return OMPI_AMD_ERR_BAD_PARAM;
+    p2p_state *p = comm_p2p(c);
+    if (!p || src < OMPI_AMD_ANY_SOURCE || src >= p->size) return OMPI_AMD_ERR_BAD_PARAM;
+    const int rc = record_hip(hipSetDevice(comm_device(c)), "hipSetDevice");
+    if (rc != OMPI_AMD_SUCCESS) return rc;
+    auto *r = new (std::nothrow) ompi_amd_p2p_request;
+    if (!r) return OMPI_AMD_ERR_BAD_PARAM;
+    r->p = p;
+    r->buf = buf;
+    r->ddt = ddt;
+    if (bytes && !is_device(buf)) {
+        r->host_dst = buf;
+        ++p->host_recvs;
+    }
+    r->cap = bytes;
+    r->src = src;
+    r->tag = tag;
+    if (p2p_trace())
+        fprintf(stderr, "[p2p %d] irecv req %p cap %zu src %d tag %d\n", p->rank, (void *)r, bytes, src, tag);
+    r->stream = comm_call_stream(c, stream);
+    std::lock_guard<std::recursive_mutex> g(p->mu);
+    p->recvs.push_back(r);
+    progress(p);
+    *out = r;
+    return OMPI_AMD_SUCCESS;
+}
+
+// What the typed forms refuse beyond the byte forms, before any device work:
+// a host buffer, a datatype that is no device program or has a negative
+// extent, count * size past SIZE_MAX.  *bytes: the packed message (ddt NULL:
+// count bytes).
+static int typed_bytes(const void *buf, size_t count, const ompi_amd_ddt_t *ddt, size_t *bytes) {
+    size_t size = 1;
+    if (ddt && count && !p2p_type_of(ddt, &size)) return OMPI_AMD_ERR_BAD_PARAM;  // count 0 ignores it
+    if (__builtin_mul_overflow(count, size, bytes)) return OMPI_AMD_ERR_BAD_PARAM;
+    if (buf && !is_device(buf)) return OMPI_AMD_ERR_BAD_PARAM;
+    return OMPI_AMD_SUCCESS;
+}
+
+// The blocking forms' second halves.
+static int recv_wait(ompi_amd_p2p_request_t *r, ompi_amd_status_t *st) {
+    int rc = wait_one(r);
+    if (rc != OMPI_AMD_SUCCESS && !r->done) cancel_recv(r);  // one timeout, not two
+    fill_status(r, st);
+    const int frc = ompi_amd_p2p_free(r);
+    return rc != OMPI_AMD_SUCCESS ? rc : frc;
+}
+
+static int sendrecv_wait(ompi_amd_p2p_request_t *rr, ompi_amd_p2p_request_t *sr, ompi_amd_status_t *st) {
+    const int rrc = wait_one(rr);
+    if (rrc != OMPI_AMD_SUCCESS && !rr->done) cancel_recv(rr);
+    fill_status(rr, st);
+    const int src_ = wait_one(sr);
+    (void)ompi_amd_p2p_free(rr);
+    (void)ompi_amd_p2p_free(sr);
+    return rrc != OMPI_AMD_SUCCESS ? rrc : src_;
+}
+
 }  // namespace ompi_amd
 
 extern "C" {
@@ -867,20 +1021,9 @@ int ompi_amd_isend(ompi_amd_comm_t *c, const void *buf, size_t bytes, int dst, i
     pair_q &q = p->pair(p->rank, dst);
     const uint64_t seq = q.posted.load(std::memory_order_relaxed);
     msg_slot &m = q.slot[seq % kSlots];
-    // the ring slot must be free: its previous message completed (DONE) or
-    // was never used; wait for the receiver otherwise (bounded only by
-    // p2p_timeout_ms)
-    const double t0 = now_s();
-    for (;;) {
-        const uint32_t st = m.state.load(std::memory_order_acquire);
-        if (st == S_FREE || st == S_DONE) break;
-        progress(p);  // our own receives keep flowing meanwhile
-        sched_yield();
-        if (over(p, t0)) {
-            record_msg("p2p send to %d: %d messages unmatched for %.1f s", dst, kSlots, limit_s(p));
-            delete r;
-            return OMPI_AMD_ERR_TIMEOUT;
-        }
+    if (!slot_free(p, m, dst)) {
+        delete r;
+        return OMPI_AMD_ERR_TIMEOUT;
     }
     reclaim(p);
     const void *src = buf;
@@ -1018,18 +1161,8 @@ int ompi_amd_isend(ompi_amd_comm_t *c, const void *buf, size_t bytes, int dst, i
         delete r;
         return rc;
     }
-    m.tag = tag;
-    m.seq = seq;
-    m.bytes = bytes;
-    m.raw = hstaged ? hoff : reinterpret_cast<uint64_t>(src);
-    m.d = d;
-    m.fd = fd;
-    m.inl = inl ? 1u : hstaged ? 2u : flagged ? 3u : sflagged ? 4u : 0u;
-    if (p2p_trace())
-        fprintf(stderr, "[p2p %d] post -> dst %d seq %llu tag %d bytes %zu inl %u\n", p->rank, dst,
-                (unsigned long long)seq, tag, bytes, m.inl);
-    m.state.store(S_POSTED, std::memory_order_release);
-    q.posted.store(seq + 1, std::memory_order_release);
+    post(p, q, m, dst, seq, tag, bytes, hstaged ? hoff : reinterpret_cast<uint64_t>(src), d, fd,
+         inl ? 1u : hstaged ? 2u : flagged ? 3u : sflagged ? 4u : 0u);
     r->seq = seq;
     // the user's buffer is free again once staged (Ssend: at the FIN)
     // (a device eager send: once its copy kernel ran, test_one)
@@ -1040,30 +1173,7 @@ int ompi_amd_isend(ompi_amd_comm_t *c, const void *buf, size_t bytes, int dst, i
 
 int ompi_amd_irecv(ompi_amd_comm_t *c, void *buf, size_t bytes, int src, int tag, void *stream,
                    ompi_amd_p2p_request_t **out) {
-    if (!c || !out || (bytes && !buf) || tag < OMPI_AMD_ANY_TAG) return OMPI_AMD_ERR_BAD_PARAM;
-    p2p_state *p = comm_p2p(c);
-    if (!p || src < OMPI_AMD_ANY_SOURCE || src >= p->size) return OMPI_AMD_ERR_BAD_PARAM;
-    const int rc = record_hip(hipSetDevice(comm_device(c)), "hipSetDevice");
-    if (rc != OMPI_AMD_SUCCESS) return rc;
-    auto *r = new (std::nothrow) ompi_amd_p2p_request;
-    if (!r) return OMPI_AMD_ERR_BAD_PARAM;
-    r->p = p;
-    r->buf = buf;
-    if (bytes && !is_device(buf)) {
-        r->host_dst = buf;
-        ++p->host_recvs;
-    }
-    r->cap = bytes;
-    r->src = src;
-    r->tag = tag;
-    if (p2p_trace())
-        fprintf(stderr, "[p2p %d] irecv req %p cap %zu src %d tag %d\n", p->rank, (void *)r, bytes, src, tag);
-    r->stream = comm_call_stream(c, stream);
-    std::lock_guard<std::recursive_mutex> g(p->mu);
-    p->recvs.push_back(r);
-    progress(p);
-    *out = r;
-    return OMPI_AMD_SUCCESS;
+    return post_recv(c, buf, bytes, nullptr, src, tag, stream, out);
 }
 
 int ompi_amd_p2p_test(ompi_amd_p2p_request_t *r, int *done, ompi_amd_status_t *st) {
@@ -1110,13 +1220,8 @@ int ompi_amd_send(ompi_amd_comm_t *c, const void *buf, size_t bytes, int dst, in
 int ompi_amd_recv(ompi_amd_comm_t *c, void *buf, size_t bytes, int src, int tag, void *stream,
                   ompi_amd_status_t *st) {
     ompi_amd_p2p_request_t *r = nullptr;
-    int rc = ompi_amd_irecv(c, buf, bytes, src, tag, stream, &r);
-    if (rc != OMPI_AMD_SUCCESS) return rc;
-    rc = wait_one(r);
-    if (rc != OMPI_AMD_SUCCESS && !r->done) cancel_recv(r);  // one timeout, not two
-    fill_status(r, st);
-    const int frc = ompi_amd_p2p_free(r);
-    return rc != OMPI_AMD_SUCCESS ? rc : frc;
+    const int rc = ompi_amd_irecv(c, buf, bytes, src, tag, stream, &r);
+    return rc != OMPI_AMD_SUCCESS ? rc : recv_wait(r, st);
 }
 
 int ompi_amd_sendrecv(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, int dst, int stag,
@@ -1130,13 +1235,166 @@ int ompi_amd_sendrecv(ompi_amd_comm_t *c, const void *sbuf, size_t sbytes, int d
         (void)ompi_amd_p2p_free(rr);
         return rc;
     }
-    const int rrc = wait_one(rr);
-    if (rrc != OMPI_AMD_SUCCESS && !rr->done) cancel_recv(rr);
-    fill_status(rr, st);
-    const int src_ = wait_one(sr);
-    (void)ompi_amd_p2p_free(rr);
-    (void)ompi_amd_p2p_free(sr);
-    return rrc != OMPI_AMD_SUCCESS ? rrc : src_;
+    return sendrecv_wait(rr, sr, st);
+}
+
+}  // extern "C"
+
+// ---- the typed forms ----
+// sendrecv_typed's receive, posted by its send once that send can no longer be
+// refused as UNSUPPORTED: a refused sendrecv has then matched no message.
+struct typed_recv_args {
+    void *buf;
+    size_t count;
+    const ompi_amd_ddt_t *ddt;
+    int src, tag;
+    ompi_amd_p2p_request_t **out;
+};
+
+static int isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const ompi_amd_ddt_t *ddt, int dst,
+                       int tag, int mode, void *stream, ompi_amd_p2p_request_t **out,
+                       const typed_recv_args *with) {
+    auto post_with = [&]() {
+        return with ? ompi_amd_irecv_typed(c, with->buf, with->count, with->ddt, with->src, with->tag, stream,
+                                           with->out)
+                    : OMPI_AMD_SUCCESS;
+    };
+    size_t bytes = 0;
+    int rc = typed_bytes(buf, count, ddt, &bytes);
+    if (rc != OMPI_AMD_SUCCESS) return rc;
+    if (!ddt || !bytes) {  // a byte send: only MPI_Bsend is UNSUPPORTED, and sendrecv sends standard
+        rc = post_with();
+        return rc != OMPI_AMD_SUCCESS ? rc : ompi_amd_isend(c, buf, bytes, dst, tag, mode, stream, out);
+    }
+    if (!c || !out || tag < 0 || !buf) return OMPI_AMD_ERR_BAD_PARAM;
+    p2p_state *p = comm_p2p(c);
+    if (!p || dst < 0 || dst >= p->size) return OMPI_AMD_ERR_BAD_PARAM;
+    if (mode == OMPI_AMD_SEND_BUFFERED) {
+        record_msg("MPI_Bsend of device buffers is not provided");
+        return OMPI_AMD_ERR_UNSUPPORTED;
+    }
+    if (mode < OMPI_AMD_SEND_SYNCHRONOUS || mode > OMPI_AMD_SEND_STANDARD)
+        return OMPI_AMD_ERR_BAD_PARAM;
+    std::lock_guard<std::recursive_mutex> g(p->mu);
+    if (p->user_ipc) return OMPI_AMD_ERR_UNSUPPORTED;  // no typed rendezvous: the caller packs
+    rc = record_hip(hipSetDevice(comm_device(c)), "hipSetDevice");
+    if (rc == OMPI_AMD_SUCCESS) rc = eager_area(p);
+    if (rc != OMPI_AMD_SUCCESS) return rc;
+    const hipStream_t s = comm_call_stream(c, stream);
+    const bool eager = bytes <= kEager;
+    stage st;
+    reclaim(p);
+    if (!eager && !take_stage(p, p->send_free, bytes, true, &st)) return OMPI_AMD_ERR_UNSUPPORTED;
+    rc = post_with();
+    if (rc != OMPI_AMD_SUCCESS) {
+        if (!eager) p->send_free.push_back(st);
+        return rc;
+    }
+    auto *r = new (std::nothrow) ompi_amd_p2p_request;
+    pair_q &q = p->pair(p->rank, dst);
+    const uint64_t seq = q.posted.load(std::memory_order_relaxed);
+    msg_slot &m = q.slot[seq % kSlots];
+    if (!r || !slot_free(p, m, dst)) {
+        if (!eager) p->send_free.push_back(st);
+        const int erc = r ? OMPI_AMD_ERR_TIMEOUT : OMPI_AMD_ERR_BAD_PARAM;
+        delete r;
+        return erc;
+    }
+    r->p = p;
+    r->is_send = true;
+    r->peer = dst;
+    r->stream = s;
+    // The pack runs on `s` after the buffer's producers and publishes the
+    // slot's cell flag itself; the message is posted at once.  A standard
+    // send completes when the pack has run (its mark, or an event); MPI_Ssend
+    // takes neither and completes at the receiver's FIN.
+    const bool sync = mode == OMPI_AMD_SEND_SYNCHRONOUS;
+    if (!sync) take_mark(r);
+    char *cell = p->eager + ((size_t)dst * kSlots + seq % kSlots) * kCell;
+    uint64_t *flag = reinterpret_cast<uint64_t *>(cell + kEager);
+    typed_pick pick;
+    if (eager) {
+        rc = eager_put_typed(ddt, buf, cell, bytes, comm_typed_force64(c), flag, seq + 1, r->mark, r->mark_v,
+                             s, &pick);
+    } else {
+        xfer_sig sg;
+        sg.flag = flag;
+        sg.flag_v = seq + 1;
+        sg.done = reinterpret_cast<uint32_t *>(cell + kEager + 8);
+        sg.mark = r->mark;
+        sg.mark_v = r->mark_v;
+        rc = xfer_pack_sig(ddt, buf, st.buf, bytes, comm_typed_force64(c), s, sg, &pick);
+    }
+    if (rc == OMPI_AMD_SUCCESS && !sync && !r->mark) rc = record_copy(p, r);
+    if (rc != OMPI_AMD_SUCCESS) {
+        if (!eager) p->send_free.push_back(st);
+        if (r->ev) p->ev_free.push_back(r->ev);
+        mark_word_put(r->mark);
+        delete r;
+        return rc;
+    }
+    p->typed_granule = pick.granule;
+    p->typed_walk64 += pick.w64 ? 1 : 0;
+    if (eager) {
+        ++p->typed_eager;
+        post(p, q, m, dst, seq, tag, bytes, reinterpret_cast<uint64_t>(cell), p->cell_desc(cell), ipc_desc{}, 3u);
+    } else {
+        ++p->typed_staged;
+        p->staged.push_back({dst, seq, st});
+        post(p, q, m, dst, seq, tag, bytes, reinterpret_cast<uint64_t>(st.buf), st.d, p->cell_desc(cell), 4u);
+    }
+    r->seq = seq;
+    *out = r;
+    return OMPI_AMD_SUCCESS;
+}
+
+extern "C" {
+
+int ompi_amd_isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const ompi_amd_ddt_t *ddt,
+                         int dst, int tag, int mode, void *stream, ompi_amd_p2p_request_t **out) {
+    return isend_typed(c, buf, count, ddt, dst, tag, mode, stream, out, nullptr);
+}
+
+int ompi_amd_irecv_typed(ompi_amd_comm_t *c, void *buf, size_t count, const ompi_amd_ddt_t *ddt, int src,
+                         int tag, void *stream, ompi_amd_p2p_request_t **out) {
+    size_t bytes = 0;
+    const int rc = typed_bytes(buf, count, ddt, &bytes);
+    if (rc != OMPI_AMD_SUCCESS) return rc;
+    return post_recv(c, buf, bytes, bytes ? ddt : nullptr, src, tag, stream, out);
+}
+
+int ompi_amd_send_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const ompi_amd_ddt_t *ddt,
+                        int dst, int tag, int mode, void *stream) {
+    ompi_amd_p2p_request_t *r = nullptr;
+    const int rc = ompi_amd_isend_typed(c, buf, count, ddt, dst, tag, mode, stream, &r);
+    return rc != OMPI_AMD_SUCCESS ? rc : ompi_amd_p2p_free(r);
+}
+
+int ompi_amd_recv_typed(ompi_amd_comm_t *c, void *buf, size_t count, const ompi_amd_ddt_t *ddt, int src,
+                        int tag, void *stream, ompi_amd_status_t *st) {
+    ompi_amd_p2p_request_t *r = nullptr;
+    const int rc = ompi_amd_irecv_typed(c, buf, count, ddt, src, tag, stream, &r);
+    return rc != OMPI_AMD_SUCCESS ? rc : recv_wait(r, st);
+}
+
+int ompi_amd_sendrecv_typed(ompi_amd_comm_t *c, const void *sbuf, size_t scount,
+                            const ompi_amd_ddt_t *sddt, int dst, int stag, void *rbuf, size_t rcount,
+                            const ompi_amd_ddt_t *rddt, int src, int rtag, void *stream,
+                            ompi_amd_status_t *st) {
+    // Both are posted before either is waited on, the receive by the send
+    // itself once it cannot be refused any more: on UNSUPPORTED (the caller
+    // packs and calls again) no receive was posted and no message matched.
+    ompi_amd_p2p_request_t *rr = nullptr, *sr = nullptr;
+    const typed_recv_args with{rbuf, rcount, rddt, src, rtag, &rr};
+    const int rc = isend_typed(c, sbuf, scount, sddt, dst, stag, OMPI_AMD_SEND_STANDARD, stream, &sr, &with);
+    if (rc != OMPI_AMD_SUCCESS) {  // past the receive only a failed launch or a full ring's timeout
+        if (rr) {
+            cancel_recv(rr);
+            (void)ompi_amd_p2p_free(rr);
+        }
+        return rc;
+    }
+    return sendrecv_wait(rr, sr, st);
 }
 
 int ompi_amd_iprobe(ompi_amd_comm_t *c, int src, int tag, int *flag, ompi_amd_status_t *st) {

@@ -283,7 +283,7 @@ static void stage_free(mca_pml_rocm_request_t *r)
  * is packed on the device into a pooled device buffer (one kernel: no host
  * round trip — the reference packs device data through the convertor in
  * the send path, pml_ob1_cuda.c:56-101); a host one is packed on the host */
-static int stage_for(mca_pml_rocm_request_t *r, int fill)
+static int pack_for(mca_pml_rocm_request_t *r, int fill)
 {
     r->bytes = type_bytes(r->dtype, r->count);
     r->stage = NULL;
@@ -313,6 +313,61 @@ static int stage_for(mca_pml_rocm_request_t *r, int fill)
     return OMPI_SUCCESS;
 }
 
+static void *lib_buf(mca_pml_rocm_request_t *r) { return NULL != r->stage ? r->stage : r->buf; }
+
+#ifdef ROCM_HAVE_TYPED_P2P
+const ompi_amd_ddt_t *opal_rocm_device_ddt(const struct opal_datatype_t *dt);
+#endif
+
+/* With ROCM_HAVE_TYPED_P2P a device buffer of a non-contiguous type that has
+ * a device program goes to the library's typed calls as it is (r->typed):
+ * their kernels walk the datatype, so there is no pooled packing buffer and
+ * no pack or unpack launch.  Every other buffer is packed as above. */
+static int stage_for(mca_pml_rocm_request_t *r, int fill)
+{
+#ifdef ROCM_HAVE_TYPED_P2P
+    r->typed = NULL;
+    if (0 != type_bytes(r->dtype, r->count) &&
+        !ompi_datatype_is_contiguous_memory_layout(r->dtype, (int) r->count) &&
+        ompi_amd_is_device_pointer(r->buf) &&
+        NULL != (r->typed = opal_rocm_device_ddt(OPAL_DT(r->dtype)))) {
+        r->bytes = type_bytes(r->dtype, r->count);
+        r->stage = NULL;
+        r->stage_dev = 0;
+        return OMPI_SUCCESS;
+    }
+#endif
+    return pack_for(r, fill);
+}
+
+/* the library's send / receive of r as stage_for left it; a typed send the
+ * library has no route for (OMPI_AMD_ERR_UNSUPPORTED: p2p_user_ipc, or no
+ * send stage left) is packed and sent as bytes */
+static int lib_isend(ompi_amd_comm_t *dev, mca_pml_rocm_request_t *r, int dst, int tag, int mode,
+                     ompi_amd_p2p_request_t **lib)
+{
+#ifdef ROCM_HAVE_TYPED_P2P
+    if (NULL != r->typed) {
+        const int rc = ompi_amd_isend_typed(dev, r->buf, r->count, r->typed, dst, tag, mode, NULL, lib);
+        if (OMPI_AMD_ERR_UNSUPPORTED != rc) return rc;
+        r->typed = NULL;
+        if (OMPI_SUCCESS != pack_for(r, 1)) return OMPI_AMD_ERR_HIP;
+    }
+#endif
+    return ompi_amd_isend(dev, lib_buf(r), r->bytes, dst, tag, mode, NULL, lib);
+}
+
+static int lib_irecv(ompi_amd_comm_t *dev, mca_pml_rocm_request_t *r, int src, int tag,
+                     ompi_amd_p2p_request_t **lib)
+{
+    src = MPI_ANY_SOURCE == src ? OMPI_AMD_ANY_SOURCE : src;
+    tag = MPI_ANY_TAG == tag ? OMPI_AMD_ANY_TAG : tag;
+#ifdef ROCM_HAVE_TYPED_P2P
+    if (NULL != r->typed) return ompi_amd_irecv_typed(dev, r->buf, r->count, r->typed, src, tag, NULL, lib);
+#endif
+    return ompi_amd_irecv(dev, lib_buf(r), r->bytes, src, tag, NULL, lib);
+}
+
 /* a packed receive's `got` bytes back into the user's layout (whole
  * elements: a short message fills a prefix of them) */
 static int unstage_recv(mca_pml_rocm_request_t *r, size_t got)
@@ -330,8 +385,6 @@ static int unstage_recv(mca_pml_rocm_request_t *r, size_t got)
                ? OMPI_SUCCESS
                : OMPI_ERROR;
 }
-
-static void *lib_buf(mca_pml_rocm_request_t *r) { return NULL != r->stage ? r->stage : r->buf; }
 
 /* ------------------------------------------- the saved PML, device buffers */
 
@@ -585,11 +638,9 @@ static int post(mca_pml_rocm_request_t *r)
     rc = stage_for(r, r->is_send);
     if (OMPI_SUCCESS != rc) return rc;
     if (r->is_send) {
-        rc = ompi_amd_isend(dev, lib_buf(r), r->bytes, r->peer, r->tag, r->mode, NULL, &r->lib);
+        rc = lib_isend(dev, r, r->peer, r->tag, r->mode, &r->lib);
     } else {
-        rc = ompi_amd_irecv(dev, lib_buf(r), r->bytes,
-                            MPI_ANY_SOURCE == r->peer ? OMPI_AMD_ANY_SOURCE : r->peer,
-                            MPI_ANY_TAG == r->tag ? OMPI_AMD_ANY_TAG : r->tag, NULL, &r->lib);
+        rc = lib_irecv(dev, r, r->peer, r->tag, &r->lib);
     }
     if (OMPI_AMD_SUCCESS != rc) {
         stage_free(r);
@@ -849,7 +900,7 @@ static int rocm_send(const void *buf, size_t count, struct ompi_datatype_t *dtyp
     r.dtype = dtype;
     rc = stage_for(&r, 1);
     if (OMPI_SUCCESS != rc) return rc;
-    rc = rocm_err(ompi_amd_isend(dev, lib_buf(&r), r.bytes, dst, tag, (int) mode, NULL, &lib));
+    rc = rocm_err(lib_isend(dev, &r, dst, tag, (int) mode, &lib));
     if (OMPI_SUCCESS == rc) {
         rc = rocm_err(wait_lib(lib, &s));
         (void) ompi_amd_p2p_free(lib);
@@ -886,9 +937,7 @@ static int rocm_recv(void *buf, size_t count, struct ompi_datatype_t *dtype, int
     r.dtype = dtype;
     rc = stage_for(&r, 0);
     if (OMPI_SUCCESS != rc) return rc;
-    rc = rocm_err(ompi_amd_irecv(dev, lib_buf(&r), r.bytes,
-                                 MPI_ANY_SOURCE == src ? OMPI_AMD_ANY_SOURCE : src,
-                                 MPI_ANY_TAG == tag ? OMPI_AMD_ANY_TAG : tag, NULL, &lib));
+    rc = rocm_err(lib_irecv(dev, &r, src, tag, &lib));
     if (OMPI_SUCCESS == rc) {
         rc = rocm_err(wait_lib(lib, &s));
         (void) ompi_amd_p2p_free(lib);

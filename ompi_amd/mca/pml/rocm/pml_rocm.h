@@ -75,6 +75,11 @@ typedef struct mca_pml_rocm_request_t {
     void *stage;
     int stage_dev;
     size_t bytes;
+#ifdef ROCM_HAVE_TYPED_P2P
+    /* a device buffer of a non-contiguous type whose device program the
+     * library's typed point-to-point calls walk themselves: no stage */
+    const ompi_amd_ddt_t *typed;
+#endif
     /* a device buffer on the saved PML: its request, and the host copy of
      * the buffer's typed span it runs on (hspan - hgap = the typed base) */
     ompi_request_t *inner;

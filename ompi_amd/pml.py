@@ -8,10 +8,11 @@ Mirrors the PML module entry points (ompi/mca/pml/pml.h):
     pml_send / pml_recv                                           pml.h:341-349, 262-270
     pml_iprobe / pml_probe                                        pml.h:371-377, 398-403
 
-with the message size in bytes (contiguous data; non-contiguous datatypes
-go through ompi_amd.datatype's convertor first).  The receiver pulls the
-sender's buffer over xGMI through its IPC mapping (include/ompi_amd_p2p.h);
-there is no host fallback for device buffers.
+with the message size in bytes, or, in the ``*_typed`` forms, a count of
+elements of an ``ompi_amd.datatype.Datatype`` that the kernels moving the
+message walk themselves (no packed copy; device buffers only).  The receiver
+pulls the sender's buffer over xGMI through its IPC mapping
+(include/ompi_amd_p2p.h); there is no host fallback for device buffers.
 """
 from __future__ import annotations
 
@@ -51,8 +52,9 @@ def _nbytes(buf, nbytes):
 class P2PRequest:
     """MPI_Request of an isend / irecv."""
 
-    def __init__(self, comm: Communicator, handle, what: str):
+    def __init__(self, comm: Communicator, handle, what: str, ddt=None):
         self._comm, self._h, self._what = comm, handle, what
+        self._ddt = ddt  # a typed request keeps its datatype's program alive
         self.status: Status | None = None
 
     def test(self) -> bool:
@@ -112,6 +114,50 @@ def sendrecv(comm: Communicator, sbuf, dst: int, stag: int, rbuf, src: int, rtag
     _lib.check(comm._lib.ompi_amd_sendrecv(comm._h, _ptr(sbuf), _nbytes(sbuf, sbytes), dst, stag,
                                            _ptr(rbuf), _nbytes(rbuf, rbytes), src, rtag,
                                            _stream(stream), ctypes.byref(st)), "sendrecv")
+    return _status(st)
+
+
+def _ddt(t):
+    return None if t is None else t.commit()._handle
+
+
+def isend_typed(comm: Communicator, buf, count: int, ddt, dst: int, tag: int,
+                mode: int = SEND_STANDARD, stream=None) -> P2PRequest:
+    """isend of `count` elements of `ddt` (None: bytes) based at `buf`."""
+    h = ctypes.c_void_p()
+    _lib.check(comm._lib.ompi_amd_isend_typed(comm._h, _ptr(buf), count, _ddt(ddt), dst, tag, mode,
+                                              _stream(stream), ctypes.byref(h)), "isend_typed")
+    return P2PRequest(comm, h, f"isend_typed(to {dst}, tag {tag})", ddt)
+
+
+def irecv_typed(comm: Communicator, buf, count: int, ddt, src: int = ANY_SOURCE, tag: int = ANY_TAG,
+                stream=None) -> P2PRequest:
+    h = ctypes.c_void_p()
+    _lib.check(comm._lib.ompi_amd_irecv_typed(comm._h, _ptr(buf), count, _ddt(ddt), src, tag,
+                                              _stream(stream), ctypes.byref(h)), "irecv_typed")
+    return P2PRequest(comm, h, f"irecv_typed(from {src}, tag {tag})", ddt)
+
+
+def send_typed(comm: Communicator, buf, count: int, ddt, dst: int, tag: int,
+               mode: int = SEND_STANDARD, stream=None) -> None:
+    _lib.check(comm._lib.ompi_amd_send_typed(comm._h, _ptr(buf), count, _ddt(ddt), dst, tag, mode,
+                                             _stream(stream)), "send_typed")
+
+
+def recv_typed(comm: Communicator, buf, count: int, ddt, src: int = ANY_SOURCE, tag: int = ANY_TAG,
+               stream=None) -> Status:
+    st = _lib.Status()
+    _lib.check(comm._lib.ompi_amd_recv_typed(comm._h, _ptr(buf), count, _ddt(ddt), src, tag,
+                                             _stream(stream), ctypes.byref(st)), "recv_typed")
+    return _status(st)
+
+
+def sendrecv_typed(comm: Communicator, sbuf, scount: int, sddt, dst: int, stag: int, rbuf, rcount: int,
+                   rddt, src: int, rtag: int, stream=None) -> Status:
+    st = _lib.Status()
+    _lib.check(comm._lib.ompi_amd_sendrecv_typed(comm._h, _ptr(sbuf), scount, _ddt(sddt), dst, stag,
+                                                 _ptr(rbuf), rcount, _ddt(rddt), src, rtag,
+                                                 _stream(stream), ctypes.byref(st)), "sendrecv_typed")
     return _status(st)
 
 
