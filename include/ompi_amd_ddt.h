@@ -4,7 +4,9 @@
  * Replaces the convertor's per-run memcpy / cuMemcpy on device memory
  * (opal/datatype/opal_datatype_pack.h:37-206, opal_datatype_unpack.c:
  * 245-428, opal/datatype/opal_datatype_cuda.c:121-145: one cuMemcpy per
- * contiguous block) with one kernel launch per convertor call.
+ * contiguous block) with one kernel launch per convertor call, and
+ * ompi_datatype_sndrcv (ompi/datatype/ompi_datatype_sndrcv.c) with one launch
+ * that walks both datatypes (ompi_amd_ddt_sndrcv).
  */
 #ifndef OMPI_AMD_DDT_H
 #define OMPI_AMD_DDT_H
@@ -118,6 +120,38 @@ enum {
  * returns OMPI_AMD_DDT_ROUTE_SLOTS. */
 int ompi_amd_ddt_route_counts(int64_t *out, int n);
 void ompi_amd_ddt_route_reset(void);
+
+/* ompi_datatype_sndrcv (ompi/datatype/ompi_datatype_sndrcv.c) for device
+ * buffers: the packed stream of `scount` elements of `sddt` based at `sbuf`
+ * is written through `rddt` based at `rbuf`, in ONE kernel that gathers
+ * through the one program and scatters through the other — no packed copy
+ * exists anywhere.  A NULL datatype means bytes (count =
+ * bytes): with one end contiguous the call is the one-ended walk, with both
+ * one copy.  A send side longer than rcount * size(rddt) writes the
+ * capacity's bytes and returns OMPI_AMD_ERR_TRUNCATE; a shorter one writes
+ * exactly its bytes (the stream may end inside a receive element).  Bytes
+ * rddt does not own are never written.  Stream-ordered, one launch, no
+ * communicator.  OMPI_AMD_ERR_BAD_PARAM, before any device work: a NULL
+ * buffer with a non-zero count, a host pointer, a negative extent, count *
+ * size past SIZE_MAX, a handle that is no device program.  Overlapping
+ * source and destination are the caller's error, as in the reference. */
+int ompi_amd_ddt_sndrcv(const void *sbuf, size_t scount, const ompi_amd_ddt_t *sddt,
+                        void *rbuf, size_t rcount, const ompi_amd_ddt_t *rddt, void *stream);
+/* What the calls with a datatype on both ends launched, process-wide (the
+ * one-ended and plain routes move nothing here). */
+enum {
+    OMPI_AMD_DDT_SNDRCV_LAUNCHES = 0, /* launches of the two-ended kernel */
+    OMPI_AMD_DDT_SNDRCV_BOTH_LDS,     /* those with both programs in LDS */
+    OMPI_AMD_DDT_SNDRCV_WALK64,       /* those that ran the 64-bit walk */
+    OMPI_AMD_DDT_SNDRCV_GRANULE,      /* the last launch's granule (bytes) */
+    OMPI_AMD_DDT_SNDRCV_SLOTS
+};
+/* Copies min(n, OMPI_AMD_DDT_SNDRCV_SLOTS) slots into out (NULL: none);
+ * returns OMPI_AMD_DDT_SNDRCV_SLOTS. */
+int ompi_amd_ddt_sndrcv_counts(int64_t *out, int n);
+/* Test hook: non-zero makes every later ompi_amd_ddt_sndrcv run the 64-bit
+ * walk (what param "typed_force64" is to a communicator's calls). */
+void ompi_amd_ddt_sndrcv_force64(int on);
 
 #ifdef __cplusplus
 }

@@ -47,11 +47,25 @@
  * scatters into the receive layout.  On the wire a message
  * is its packed stream, so `bytes` in a status or a probe is packed bytes,
  * matching is unchanged, and a typed call on one side meets a byte call, or
- * a different datatype of the same packed length, on the other.  There is no
- * typed rendezvous: with "p2p_user_ipc" = 1, or when the pool has no stage
- * left, a typed send returns OMPI_AMD_ERR_UNSUPPORTED before it took
- * anything, and the MCA glue packs non-contiguous datatypes first as it
- * does for host buffers.
+ * a different datatype of the same packed length, on the other.
+ *
+ * Typed rendezvous.  A typed message to a peer that is
+ * larger than 4 KiB packed and takes no stage goes out of the caller's buffer
+ * as it lies: with "p2p_user_ipc" = 1 (a message of at most 4 KiB still goes
+ * through the eager cell), or when the pool has no stage left.  The sender
+ * copies its element program into the slot's eager cell, waits for the
+ * buffer's producers, exports the allocation and posts; the receiver maps
+ * buffer and program and runs one kernel that gathers through the sender's
+ * datatype and scatters through its own (a byte receive: the one-ended pack
+ * walk).  The send completes at the receiver's FIN.  It needs a program of at
+ * most 39 elements (4 KiB of cell) and a buffer whose allocation peers can map
+ * (an IPC-safe size, not older than an IPC close); without these a send under
+ * "p2p_user_ipc" = 1 tries a stage, and a send that gets neither returns
+ * OMPI_AMD_ERR_UNSUPPORTED before it took anything — the MCA glue then packs
+ * non-contiguous datatypes first as it does for host buffers.  Messages to
+ * self keep their behaviour exactly: a typed send to the own rank is refused
+ * with OMPI_AMD_ERR_UNSUPPORTED under "p2p_user_ipc" = 1 and when the pool has
+ * no stage left.
  */
 #ifndef OMPI_AMD_P2P_H
 #define OMPI_AMD_P2P_H
@@ -117,7 +131,11 @@ int ompi_amd_sendrecv(ompi_amd_comm_t *comm, const void *sbuf, size_t sbytes, in
  * by path), p2p_typed_recv (receives whose copy-out walked a datatype),
  * p2p_typed_lds (those with the program in LDS), p2p_typed_granule (access
  * width of the last typed launch), p2p_typed_walk64 (typed launches that ran
- * the 64-bit walk; "typed_force64" forces it).  A typed staged send does not
+ * the 64-bit walk; "typed_force64" forces it), p2p_typed_rndv (sends that
+ * went by typed rendezvous; they count in neither p2p_typed_staged nor
+ * p2p_typed_eager), p2p_typed_sndrcv (receives that ran the kernel with a
+ * datatype on both ends; they count in p2p_typed_recv too, and in
+ * p2p_typed_lds when both programs were in LDS).  A typed staged send does not
  * count in p2p_staged_sends.  sendrecv_typed posts its receive only once its
  * send can no longer be refused: after OMPI_AMD_ERR_UNSUPPORTED it has
  * matched no message. */

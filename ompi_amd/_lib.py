@@ -114,6 +114,10 @@ PROTOTYPES = [
       _C.POINTER(_C.c_size_t), _C.c_void_p]),
     ("ompi_amd_ddt_route_counts", _C.c_int, [_C.POINTER(_C.c_int64), _C.c_int]),
     ("ompi_amd_ddt_route_reset", None, []),
+    ("ompi_amd_ddt_sndrcv", _C.c_int,
+     [_C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_void_p]),
+    ("ompi_amd_ddt_sndrcv_counts", _C.c_int, [_C.POINTER(_C.c_int64), _C.c_int]),
+    ("ompi_amd_ddt_sndrcv_force64", None, [_C.c_int]),
     ("ompi_amd_is_device_pointer", _C.c_int, [_C.c_void_p]),
     ("ompi_amd_pointer_range", _C.c_int, [_C.c_void_p, _C.POINTER(_C.c_void_p), _C.POINTER(_C.c_size_t)]),
     ("ompi_amd_memcpy_async", _C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
@@ -452,3 +456,16 @@ def ddt_route_counts() -> dict:
 
 def ddt_route_reset() -> None:
     load().ompi_amd_ddt_route_reset()
+
+
+# slots of ompi_amd_ddt_sndrcv_counts, in the order of include/ompi_amd_ddt.h
+DDT_SNDRCV_SLOTS = ["launches", "both_lds", "walk64", "granule"]
+
+
+def ddt_sndrcv_counts() -> dict:
+    """Launches of the two-ended datatype kernel by ompi_amd_ddt_sndrcv, those
+    with both programs in LDS, those on the 64-bit walk, the last granule."""
+    out = (ctypes.c_int64 * len(DDT_SNDRCV_SLOTS))()
+    n = load().ompi_amd_ddt_sndrcv_counts(out, len(DDT_SNDRCV_SLOTS))
+    assert n == len(DDT_SNDRCV_SLOTS), n
+    return dict(zip(DDT_SNDRCV_SLOTS, [int(v) for v in out]))

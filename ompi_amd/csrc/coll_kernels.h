@@ -997,11 +997,80 @@ __device__ __forceinline__ void typed_pipe_copy(const typed_end &e, char *typed,
     }
 }
 
+// typed_walk with a datatype on both ends: ng G-byte
+// granules from stream byte lo on, gathered through se based at sb and
+// scattered through re based at rb.  The two programs share nothing: each has
+// its own table, size and divisors.  Per pass a lane resolves kDdtUnroll
+// source and as many destination addresses, issues all the loads, then the
+// stores.  The stores are plain: the destination is this GPU's memory wherever
+// the walk is used.
+template <int G>
+__device__ __forceinline__ void typed_walk2(const typed_end &se, const typed_end &re, const char *sb, char *rb,
+                                            int64_t lo, int64_t ng, bool w64) {
+    using T = typename granule<G>::t;
+    constexpr int U = kDdtUnroll, S = kXferThreads;
+    constexpr int LG = G == 16 ? 4 : G == 8 ? 3 : G == 4 ? 2 : G == 2 ? 1 : 0;
+    const ddt_elem *sel = se.d.elems, *rel = re.d.elems;
+    const int sn = se.d.nelem, rn = re.d.nelem;
+    const uint32_t ssize_g = (uint32_t)(se.d.size >> LG), rsize_g = (uint32_t)(re.d.size >> LG);
+    const fastdiv ssdiv = se.sdiv[LG], rsdiv = re.sdiv[LG];
+    for (int64_t j0 = threadIdx.x; j0 < ng; j0 += (int64_t)S * U) {
+        int64_t soff[U], roff[U];
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t j = j0 + u * S;
+            if (j < ng) {
+                soff[u] = w64 ? typed_offset<int64_t>(sel, sn, se.d.size, se.d.extent, lo + j * G)
+                              : typed_offset_fast<G>(sel, sn, ssize_g, ssdiv, se.d.extent,
+                                                     (uint32_t)((lo >> LG) + j));
+                roff[u] = w64 ? typed_offset<int64_t>(rel, rn, re.d.size, re.d.extent, lo + j * G)
+                              : typed_offset_fast<G>(rel, rn, rsize_g, rsdiv, re.d.extent,
+                                                     (uint32_t)((lo >> LG) + j));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u * S < ng) v[u] = *reinterpret_cast<const T *>(sb + soff[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u * S < ng) *reinterpret_cast<T *>(rb + roff[u]) = v[u];
+    }
+}
+
+// typed_pipe_copy with a datatype on both ends: stream bytes [lo, hi) of a
+// stream of `stream` bytes, by one workgroup, from the layout of se based at
+// sb into the layout of re based at rb, with no packed copy between them.
+// Granule and walk: coll_typed.h's typed_granule2 / typed_walk64_2.  Bytes
+// past the last whole granule (a slice's tail, or a stream that ends inside
+// an element of either type) go bytewise through both programs.
+__device__ __forceinline__ void typed_pipe_copy2(const typed_end &se, const typed_end &re, const char *sb,
+                                                 char *rb, int64_t lo, int64_t hi, int64_t stream,
+                                                 bool force64) {
+    if (hi <= lo) return;
+    const int G = typed_granule2(se.gran, re.gran, (uint64_t)(uintptr_t)sb, (uint64_t)(uintptr_t)rb, (uint64_t)lo);
+    const int64_t ng = (hi - lo) / G;
+    const bool w64 = typed_walk64_2((uint64_t)stream, G, force64, (uint64_t)se.d.size, (uint64_t)re.d.size);
+    switch (G) {
+    case 16: typed_walk2<16>(se, re, sb, rb, lo, ng, w64); break;
+    case 8: typed_walk2<8>(se, re, sb, rb, lo, ng, w64); break;
+    case 4: typed_walk2<4>(se, re, sb, rb, lo, ng, w64); break;
+    case 2: typed_walk2<2>(se, re, sb, rb, lo, ng, w64); break;
+    default: typed_walk2<1>(se, re, sb, rb, lo, ng, w64); break;
+    }
+    for (int64_t p = lo + ng * G + threadIdx.x; p < hi; p += kXferThreads) {
+        const int64_t s = typed_offset<int64_t>(se.d.elems, se.d.nelem, se.d.size, se.d.extent, p);
+        const int64_t r = typed_offset<int64_t>(re.d.elems, re.d.nelem, re.d.size, re.d.extent, p);
+        rb[r] = sb[s];
+    }
+}
+
 // copy_kernel's job table with an optional datatype on one end of a job:
 // job blockIdx.y moves stream bytes [lo, hi) of its pair, workgroup
 // blockIdx.x the a2a_slice of them.  A typed end is the block's typed base,
 // a contiguous end the address of stream byte 0.  (Both ends typed never
-// meet in one job: such a block goes through a slot, §3.5.)
+// meet in one job: such a block goes through a slot, §3.5; the walk with a
+// datatype on both ends, typed_pipe_copy2, serves §3.8's callers only.)
 enum { TCP_BYTES = 0, TCP_SRC_TYPED = 1, TCP_DST_TYPED = 2 };
 struct tcp_job {
     const char *src;

@@ -36,4 +36,22 @@ OMPI_AMD_TYPED_HD inline bool typed_walk64(uint64_t pair_bytes, int G, bool forc
     return force64 || pair_bytes / (uint64_t)G >= (1ull << 32);
 }
 
+// A copy with a datatype on BOTH ends (coll_kernels.h's typed_pipe_copy2,
+// DESIGN.md §3.8) moves one granule per lane through two programs at once:
+// G divides both datatypes' granules, both typed base addresses and the
+// first stream byte of the slice, so a granule at a stream position that is a
+// multiple of G crosses a run on neither side.
+OMPI_AMD_TYPED_HD inline int typed_granule2(int64_t gran_s, int64_t gran_r, uint64_t base_s, uint64_t base_r,
+                                            uint64_t lo) {
+    const uint64_t gs = (uint64_t)(gran_s < 0 ? -gran_s : gran_s), gr = (uint64_t)(gran_r < 0 ? -gran_r : gran_r);
+    return typed_granule((int64_t)(gs | gr), base_s, base_r | lo);
+}
+
+// Its walk: the 32-bit one also needs either size in granules to fit 32
+// bits (a stream may end inside the first element of a huge datatype).
+OMPI_AMD_TYPED_HD inline bool typed_walk64_2(uint64_t stream_bytes, int G, bool force64, uint64_t size_s,
+                                             uint64_t size_r) {
+    return typed_walk64(stream_bytes, G, force64) || (size_s | size_r) / (uint64_t)G >= (1ull << 32);
+}
+
 }  // namespace ompi_amd

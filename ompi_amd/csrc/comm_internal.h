@@ -141,6 +141,26 @@ int xfer_pack_sig(const ompi_amd_ddt_t *ddt, const void *typed, void *stage, siz
                   hipStream_t s, const xfer_sig &sig, typed_pick *pick);
 int xfer_unpack_sig(const ompi_amd_ddt_t *ddt, const void *stage, void *typed, size_t bytes, bool force64,
                     hipStream_t s, const xfer_sig &sig, typed_pick *pick);
+// A datatype on both ends.  typed_prog: a program as a
+// launch names it — this process's handle (typed_prog_of), or a peer's whose
+// table is mapped here and whose scalars came in a mailbox slot (the typed
+// rendezvous).  xfer_sndrcv: `bytes` stream bytes from the layout of sp based
+// at sbase into the layout of rp based at rbase, one launch, local stores;
+// sig as xfer_unpack_sig.  pick->lds: BOTH programs were staged in LDS.
+// xfer_pack_prog: xfer_pack_sig for such a program, no signal (a byte receive
+// of a typed rendezvous message).
+constexpr size_t kTypedElemBytes = 104;  // sizeof(ddt_elem), for code that only moves a table
+struct typed_prog {
+    const void *elems = nullptr;  // device table of ddt_elem (ddt_device.h)
+    int nelem = 0;
+    int gran = 1;
+    int64_t size = 0, extent = 0;
+};
+bool typed_prog_of(const ompi_amd_ddt_t *ddt, typed_prog *out);
+int xfer_sndrcv(const typed_prog &sp, const void *sbase, const typed_prog &rp, void *rbase, size_t bytes,
+                bool force64, hipStream_t s, const xfer_sig &sig, typed_pick *pick);
+int xfer_pack_prog(const typed_prog &sp, const void *typed, void *dst, size_t bytes, bool force64, hipStream_t s,
+                   typed_pick *pick);
 // param "typed_force64" of c
 bool comm_typed_force64(const ompi_amd_comm_t *c);
 // Point-to-point mailboxes of the communicator (created with it).

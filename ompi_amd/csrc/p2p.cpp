@@ -67,10 +67,24 @@
 //   typed    the *_typed forms: the same wire format — a
 //            message is its packed stream — with the datatype walked by the
 //            kernel that moves it (p2p_typed.hip).  The sender packs straight
-//            into the slot's eager cell or a send stage and signals as above
-//            (no typed rendezvous: UNSUPPORTED instead); the receiver's
-//            copy-out scatters from whatever device source the message names,
-//            or from a receive stage for a host source.
+//            into the slot's eager cell or a send stage and signals as
+//            above; the receiver's copy-out scatters from whatever device
+//            source the message names, or from a receive stage for a host
+//            source.
+//   typed rendezvous: a typed message to a peer larger than
+//            kEager that takes no stage — under p2p_user_ipc = 1, or when the
+//            pool gives none — goes out from the caller's buffer as it lies:
+//            the sender copies its element program (at most kRndvElems
+//            elements) into the slot's own eager cell, which a rendezvous
+//            message does not use otherwise, waits for the buffer's producers,
+//            exports the allocation and posts buffer, cell and the program's
+//            scalars; the receiver maps both and runs ONE kernel that gathers
+//            through the sender's program and scatters through its own
+//            (p2p_typed.hip's ddt_sndrcv_kernel), or packs into a byte
+//            receive.  The send completes at the FIN.  Only for a buffer
+//            comm_ipc_safe() accepts; otherwise a stage or UNSUPPORTED as
+//            before.  Messages to self keep their behaviour exactly: they are
+//            refused under p2p_user_ipc = 1 and from an empty pool.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -114,10 +128,21 @@ struct alignas(64) msg_slot {
     ipc_desc d;    // the send buffer for peers
     uint32_t inl;  // 1: payload in `inline_data`; 2: in the sender's host stage at offset `raw`;
                    // 3: in an eager cell whose flag (cell + kEager) becomes seq + 1;
-                   // 4: in a send stage (d) whose copy kernel sets the slot's cell flag (fd)
-    ipc_desc fd;   // inl 4: the sender's eager cell of this slot (its flag word)
+                   // 4: in a send stage (d) whose copy kernel sets the slot's cell flag (fd);
+                   // 5: a typed rendezvous: in the send buffer (d), laid out by the element
+                   //    program in the cell (fd) with the scalars (rndv_prog) in `inline_data`
+    ipc_desc fd;   // inl 4, 5: the sender's eager cell of this slot (4: its flag word; 5: the program)
     char inline_data[kInline];
 };
+
+// inl 5: the sender's program beside its table (which is in the cell).  The
+// table must fit the cell: 39 elements.
+struct rndv_prog {
+    int32_t nelem, gran;
+    int64_t size, extent;
+};
+constexpr int kRndvElems = (int)(kEager / kTypedElemBytes);
+static_assert(sizeof(rndv_prog) <= kInline, "the scalars travel in inline_data");
 
 struct alignas(64) pair_q {
     std::atomic<uint64_t> posted;  // descriptors published by the sender
@@ -151,6 +176,7 @@ struct p2p_state {
     // datatype, those of them with the program in LDS, the last launch's width
     int64_t typed_eager = 0, typed_staged = 0, typed_recv = 0, typed_lds = 0, typed_granule = 0;
     int64_t typed_walk64 = 0;  // typed launches, either side, that ran the 64-bit walk
+    int64_t typed_rndv = 0, typed_sndrcv = 0;  // sends by typed rendezvous, receives by the two-ended kernel
     int rank = 0, size = 0;
     char name[256] = {0};
     pair_q *q = nullptr;
@@ -309,6 +335,8 @@ int p2p_get_param(p2p_state *p, const char *key, int64_t *v) {
     else if (!strcmp(key, "p2p_typed_lds")) *v = p->typed_lds;
     else if (!strcmp(key, "p2p_typed_granule")) *v = p->typed_granule;
     else if (!strcmp(key, "p2p_typed_walk64")) *v = p->typed_walk64;
+    else if (!strcmp(key, "p2p_typed_rndv")) *v = p->typed_rndv;
+    else if (!strcmp(key, "p2p_typed_sndrcv")) *v = p->typed_sndrcv;
     else return OMPI_AMD_ERR_UNSUPPORTED;
     return OMPI_AMD_SUCCESS;
 }
@@ -717,6 +745,28 @@ static void start_recv(p2p_state *p, ompi_amd_p2p_request *r, msg_slot *m, int s
                     sg.done = p->recv_done(s, m->seq);
                     rc = xfer_copy_sig(src, dst, n, r->stream, sg);
                 }
+            }
+        } else if (m->inl == 5) {  // a typed rendezvous: src is laid out by the sender's program
+            rndv_prog sc;
+            memcpy(&sc, m->inline_data, sizeof(sc));
+            const char *table = nullptr;
+            rc = comm_import(p->c, s, m->fd, &table, true, &r->pinned2);
+            typed_prog sp, rp;
+            sp.elems = table;
+            sp.nelem = sc.nelem;
+            sp.gran = sc.gran;
+            sp.size = sc.size;
+            sp.extent = sc.extent;
+            typed_pick pick;
+            if (rc != OMPI_AMD_SUCCESS) {
+            } else if (r->ddt && typed_prog_of(r->ddt, &rp)) {  // one kernel, a datatype on both ends
+                rc = xfer_sndrcv(sp, src, rp, dst, n, comm_typed_force64(p->c), r->stream, xfer_sig{}, &pick);
+                count_typed_recv(p, pick);
+                ++p->typed_sndrcv;
+            } else {  // a byte receive: the one-ended pack walk with the remote program
+                rc = xfer_pack_prog(sp, src, dst, n, comm_typed_force64(p->c), r->stream, &pick);
+                p->typed_granule = pick.granule;
+                p->typed_walk64 += pick.w64 ? 1 : 0;
             }
         } else if (r->ddt) {
             rc = unpack_recv(p, r, src, n, xfer_sig{});
@@ -1276,7 +1326,7 @@ static int isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const 
     if (mode < OMPI_AMD_SEND_SYNCHRONOUS || mode > OMPI_AMD_SEND_STANDARD)
         return OMPI_AMD_ERR_BAD_PARAM;
     std::lock_guard<std::recursive_mutex> g(p->mu);
-    if (p->user_ipc) return OMPI_AMD_ERR_UNSUPPORTED;  // no typed rendezvous: the caller packs
+    if (p->user_ipc && dst == p->rank) return OMPI_AMD_ERR_UNSUPPORTED;  // no typed rendezvous to self
     rc = record_hip(hipSetDevice(comm_device(c)), "hipSetDevice");
     if (rc == OMPI_AMD_SUCCESS) rc = eager_area(p);
     if (rc != OMPI_AMD_SUCCESS) return rc;
@@ -1284,10 +1334,27 @@ static int isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const 
     const bool eager = bytes <= kEager;
     stage st;
     reclaim(p);
-    if (!eager && !take_stage(p, p->send_free, bytes, true, &st)) return OMPI_AMD_ERR_UNSUPPORTED;
+    // Past the eager limit: a stage, or — under p2p_user_ipc first, otherwise
+    // when the pool gives none — the typed rendezvous, for a peer, a program
+    // that fits the cell and a buffer peers can map.  Neither: UNSUPPORTED,
+    // the last point at which this send can be refused.
+    typed_prog sp;
+    bool rndv = false;
+    auto can = [&] {  // (asked only where a stage is not the first choice: the default route pays nothing)
+        return dst != p->rank && typed_prog_of(ddt, &sp) && sp.nelem <= kRndvElems && !p->age_all &&
+               comm_ipc_safe(buf);
+    };
+    if (!eager) {
+        rndv = p->user_ipc && can();
+        if (!rndv && !take_stage(p, p->send_free, bytes, true, &st)) {
+            if (p->user_ipc || !can()) return OMPI_AMD_ERR_UNSUPPORTED;
+            rndv = true;
+        }
+    }
+    const bool staged = !eager && !rndv;
     rc = post_with();
     if (rc != OMPI_AMD_SUCCESS) {
-        if (!eager) p->send_free.push_back(st);
+        if (staged) p->send_free.push_back(st);
         return rc;
     }
     auto *r = new (std::nothrow) ompi_amd_p2p_request;
@@ -1295,7 +1362,7 @@ static int isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const 
     const uint64_t seq = q.posted.load(std::memory_order_relaxed);
     msg_slot &m = q.slot[seq % kSlots];
     if (!r || !slot_free(p, m, dst)) {
-        if (!eager) p->send_free.push_back(st);
+        if (staged) p->send_free.push_back(st);
         const int erc = r ? OMPI_AMD_ERR_TIMEOUT : OMPI_AMD_ERR_BAD_PARAM;
         delete r;
         return erc;
@@ -1304,6 +1371,28 @@ static int isend_typed(ompi_amd_comm_t *c, const void *buf, size_t count, const 
     r->is_send = true;
     r->peer = dst;
     r->stream = s;
+    if (rndv) {
+        // The program into this slot's cell (library memory, exported, free
+        // since the slot is), then the buffer's producers — the receiver reads
+        // the buffer itself — then the export; the send completes at the FIN.
+        char *cell = p->eager + ((size_t)dst * kSlots + seq % kSlots) * kCell;
+        ipc_desc d{};
+        rc = record_hip(hipMemcpyAsync(cell, sp.elems, (size_t)sp.nelem * kTypedElemBytes, hipMemcpyDeviceToDevice, s),
+                        "hipMemcpyAsync (typed rendezvous program)");
+        if (rc == OMPI_AMD_SUCCESS) rc = record_hip(hipStreamSynchronize(s), "hipStreamSynchronize (send)");
+        if (rc == OMPI_AMD_SUCCESS) rc = comm_export(c, buf, &d);
+        if (rc != OMPI_AMD_SUCCESS) {
+            delete r;
+            return rc;
+        }
+        const rndv_prog sc{sp.nelem, sp.gran, sp.size, sp.extent};
+        memcpy(m.inline_data, &sc, sizeof(sc));
+        ++p->typed_rndv;
+        post(p, q, m, dst, seq, tag, bytes, reinterpret_cast<uint64_t>(buf), d, p->cell_desc(cell), 5u);
+        r->seq = seq;
+        *out = r;
+        return OMPI_AMD_SUCCESS;
+    }
     // The pack runs on `s` after the buffer's producers and publishes the
     // slot's cell flag itself; the message is posted at once.  A standard
     // send completes when the pack has run (its mark, or an event); MPI_Ssend

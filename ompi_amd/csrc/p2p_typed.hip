@@ -14,10 +14,20 @@
 // The walk is coll_kernels.h's typed_pipe_copy (granule and 32-/64-bit choice:
 // coll_typed.h); the element program sits in LDS when it fits the alltoallw
 // kernels' budget (kA2awLdsElems) and is walked from global memory otherwise.
+//
+// One kernel has a datatype on both ends and no contiguous end at all
+// (DESIGN.md §3.8):
+//   ddt_sndrcv        typed -> typed through coll_kernels.h's typed_pipe_copy2,
+//                     both programs in the same LDS budget.  It is the local
+//                     copy ompi_amd_ddt_sndrcv (include/ompi_amd_ddt.h) and the
+//                     receiver's half of the typed rendezvous, where the source
+//                     buffer and the source program are a peer's mapped memory.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 
+#include "../../include/ompi_amd_p2p.h"
 #include "coll_kernels.h"
 #include "comm_internal.h"
 #include "runtime.h"
@@ -121,6 +131,40 @@ __global__ __launch_bounds__(kXferThreads) void xfer_unpack_sig_kernel(typed_end
     typed_pipe_copy<true>(e, typed, const_cast<char *>(stage), lo, hi, bytes, false, force64 != 0);
 }
 
+// Which of the two programs a two-ended launch stages in LDS (the host picks,
+// the kernel obeys, the counters report).
+enum { SR_LDS_SRC = 1, SR_LDS_DST = 2, SR_LDS_SAME = 4 };
+
+// Every workgroup waits for sg.wait (none: only the acquire, after which a
+// peer's program and buffer are read), stages the programs `lds` names —
+// the source's at prog, the destination's behind it, or one copy for both
+// when the two ends are one program — and moves its a2a_slice of the stream.
+// The static LDS is xfer_unpack_sig_kernel's: kA2awLdsElems elements for the
+// two programs together, so the occupancy is no worse than that kernel's.
+__global__ __launch_bounds__(kXferThreads, 6) void ddt_sndrcv_kernel(typed_end se, typed_end re, int lds,
+                                                                  const char *sbase, char *rbase, int64_t bytes,
+                                                                  int force64, xfer_sig sg) {
+    __shared__ ddt_elem prog[kA2awLdsElems];
+    if (!wait_flag(sg.wait, sg.wait_v, sg.err, sg.ticks)) return;
+    constexpr int W = (int)(sizeof(ddt_elem) / sizeof(uint64_t));
+    typed_end s = se, r = re;
+    if (lds & SR_LDS_SRC) {
+        lds_words(prog, se.d.elems, se.d.nelem * W);
+        s.d.elems = prog;
+    }
+    if (lds & SR_LDS_SAME) {
+        r.d.elems = prog;
+    } else if (lds & SR_LDS_DST) {
+        ddt_elem *at = prog + ((lds & SR_LDS_SRC) ? se.d.nelem : 0);
+        lds_words(at, re.d.elems, re.d.nelem * W);
+        r.d.elems = at;
+    }
+    __syncthreads();
+    int64_t lo, hi;
+    a2a_slice(bytes, (int)blockIdx.x, (int)gridDim.x, &lo, &hi);
+    typed_pipe_copy2(s, r, sbase, rbase, lo, hi, bytes, force64 != 0);
+}
+
 bool p2p_type_of(const ompi_amd_ddt_t *ddt, size_t *size) {
     ddt_view v;
     if (!ddt_view_of(ddt, &v) || v.d.nelem <= 0 || v.d.extent < 0 || v.d.size < 0) return false;
@@ -193,4 +237,113 @@ int xfer_unpack_sig(const ompi_amd_ddt_t *ddt, const void *stage, void *typed, s
     return record_hip(hipGetLastError(), "typed signalled unpack launch");
 }
 
+bool typed_prog_of(const ompi_amd_ddt_t *ddt, typed_prog *out) {
+    ddt_view v;
+    if (!ddt_view_of(ddt, &v) || v.d.nelem <= 0 || v.d.extent < 0 || v.d.size <= 0) return false;
+    out->elems = v.d.elems;
+    out->nelem = v.d.nelem;
+    out->gran = v.gran;
+    out->size = v.d.size;
+    out->extent = v.d.extent;
+    return true;
+}
+
+static_assert(sizeof(ddt_elem) == kTypedElemBytes, "comm_internal.h's element size");
+
+static typed_end end_of_prog(const typed_prog &p) {
+    ddt_view v{};
+    v.d = ddt_desc{static_cast<const ddt_elem *>(p.elems), p.nelem, p.size, p.extent, {0u, 0u, 0u}};
+    v.gran = p.gran;
+    return end_of(true, v);
+}
+
+int xfer_sndrcv(const typed_prog &sp, const void *sbase, const typed_prog &rp, void *rbase, size_t bytes,
+                bool force64, hipStream_t s, const xfer_sig &sig, typed_pick *pick) {
+    // both in LDS when they fit together (one copy when they are one program);
+    // otherwise the larger one is walked from global memory
+    const int ns = sp.nelem, nr = rp.nelem, K = kA2awLdsElems;
+    int lds = 0;
+    if (sp.elems == rp.elems) lds = ns <= K ? SR_LDS_SRC | SR_LDS_SAME : 0;
+    else if (ns + nr <= K) lds = SR_LDS_SRC | SR_LDS_DST;
+    else if (std::min(ns, nr) <= K) lds = ns <= nr ? SR_LDS_SRC : SR_LDS_DST;
+    pick->granule = typed_granule2(sp.gran, rp.gran, (uint64_t)(uintptr_t)sbase, (uint64_t)(uintptr_t)rbase, 0);
+    pick->lds = (lds & SR_LDS_SRC) && (lds & (SR_LDS_DST | SR_LDS_SAME));
+    pick->w64 = typed_walk64_2(bytes, pick->granule, force64, (uint64_t)sp.size, (uint64_t)rp.size);
+    hipLaunchKernelGGL(ddt_sndrcv_kernel, dim3(typed_blocks(bytes)), dim3(kXferThreads), 0, s, end_of_prog(sp),
+                       end_of_prog(rp), lds, static_cast<const char *>(sbase), static_cast<char *>(rbase),
+                       (int64_t)bytes, force64 ? 1 : 0, sig);
+    return record_hip(hipGetLastError(), "typed-to-typed copy launch");
+}
+
+int xfer_pack_prog(const typed_prog &sp, const void *typed, void *dst, size_t bytes, bool force64, hipStream_t s,
+                   typed_pick *pick) {
+    const int lds = sp.nelem <= kA2awLdsElems;
+    pick->granule = typed_granule(sp.gran, (uint64_t)(uintptr_t)typed, (uint64_t)(uintptr_t)dst);
+    pick->lds = lds != 0;
+    pick->w64 = typed_walk64(bytes, pick->granule, force64);
+    hipLaunchKernelGGL(xfer_pack_sig_kernel, dim3(typed_blocks(bytes)), dim3(kXferThreads), 0, s,
+                       end_of_prog(sp), lds, static_cast<char *>(const_cast<void *>(typed)),
+                       static_cast<char *>(dst), (int64_t)bytes, force64 ? 1 : 0, xfer_sig{});
+    return record_hip(hipGetLastError(), "typed pack launch (a peer's program)");
+}
+
+// ompi_amd_ddt_sndrcv_counts' slots, process-wide like the convertor's routes
+static std::atomic<int64_t> g_sndrcv[OMPI_AMD_DDT_SNDRCV_SLOTS];
+static std::atomic<int> g_sndrcv_force64{0};
+
 }  // namespace ompi_amd
+
+using namespace ompi_amd;
+
+extern "C" {
+
+int ompi_amd_ddt_sndrcv(const void *sbuf, size_t scount, const ompi_amd_ddt_t *sddt, void *rbuf, size_t rcount,
+                        const ompi_amd_ddt_t *rddt, void *stream) {
+    typed_prog sp, rp;
+    size_t sbytes = 0, cap = 0;
+    // a count of 0 ignores its datatype and its buffer
+    const bool st = sddt && scount, rt = rddt && rcount;
+    if ((st && !typed_prog_of(sddt, &sp)) || (rt && !typed_prog_of(rddt, &rp))) return OMPI_AMD_ERR_BAD_PARAM;
+    if (__builtin_mul_overflow(scount, st ? (size_t)sp.size : 1, &sbytes) ||
+        __builtin_mul_overflow(rcount, rt ? (size_t)rp.size : 1, &cap))
+        return OMPI_AMD_ERR_BAD_PARAM;
+    if ((sbytes && !sbuf) || (cap && !rbuf)) return OMPI_AMD_ERR_BAD_PARAM;
+    if ((sbytes && !ompi_amd_is_device_pointer(sbuf)) || (cap && !ompi_amd_is_device_pointer(rbuf)))
+        return OMPI_AMD_ERR_BAD_PARAM;
+    int rc = OMPI_AMD_SUCCESS;
+    size_t n = sbytes;
+    if (n > cap) {  // ompi_datatype_sndrcv: what fits is copied, MPI_ERR_TRUNCATE
+        n = cap;
+        rc = OMPI_AMD_ERR_TRUNCATE;
+        record_msg("ddt_sndrcv truncated: %zu bytes into %zu", sbytes, cap);
+    }
+    if (n == 0) return rc;
+    const hipStream_t s = as_stream(stream);
+    const bool force64 = g_sndrcv_force64.load(std::memory_order_relaxed) != 0;
+    typed_pick pick;
+    int lrc;
+    if (st && rt) {
+        lrc = xfer_sndrcv(sp, sbuf, rp, rbuf, n, force64, s, xfer_sig{}, &pick);
+        g_sndrcv[OMPI_AMD_DDT_SNDRCV_LAUNCHES].fetch_add(1, std::memory_order_relaxed);
+        g_sndrcv[OMPI_AMD_DDT_SNDRCV_BOTH_LDS].fetch_add(pick.lds ? 1 : 0, std::memory_order_relaxed);
+        g_sndrcv[OMPI_AMD_DDT_SNDRCV_WALK64].fetch_add(pick.w64 ? 1 : 0, std::memory_order_relaxed);
+        g_sndrcv[OMPI_AMD_DDT_SNDRCV_GRANULE].store(pick.granule, std::memory_order_relaxed);
+    } else if (st) {
+        lrc = xfer_pack_sig(sddt, sbuf, rbuf, n, force64, s, xfer_sig{}, &pick);
+    } else if (rt) {
+        lrc = xfer_unpack_sig(rddt, sbuf, rbuf, n, force64, s, xfer_sig{}, &pick);
+    } else {
+        lrc = record_hip(hipMemcpyAsync(rbuf, sbuf, n, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync (ddt_sndrcv)");
+    }
+    return lrc != OMPI_AMD_SUCCESS ? lrc : rc;
+}
+
+int ompi_amd_ddt_sndrcv_counts(int64_t *out, int n) {
+    for (int i = 0; out && i < n && i < OMPI_AMD_DDT_SNDRCV_SLOTS; ++i)
+        out[i] = g_sndrcv[i].load(std::memory_order_relaxed);
+    return OMPI_AMD_DDT_SNDRCV_SLOTS;
+}
+
+void ompi_amd_ddt_sndrcv_force64(int on) { g_sndrcv_force64.store(on ? 1 : 0, std::memory_order_relaxed); }
+
+}  // extern "C"

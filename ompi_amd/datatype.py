@@ -216,6 +216,20 @@ def _addr(buf) -> int:
     raise TypeError(type(buf))
 
 
+def sndrcv(sbuf, scount: int, sddt, rbuf, rcount: int, rddt, stream=None) -> None:
+    """ompi_datatype_sndrcv (ompi/datatype/ompi_datatype_sndrcv.c) on device
+    buffers: `scount` elements of `sddt` at `sbuf` into `rcount` of `rddt` at
+    `rbuf`, one kernel launch with both datatypes walked in it and no packed
+    copy.  A datatype of None means bytes.  Raises OmpiAmdError with
+    ERR_TRUNCATE when the send side is longer (the capacity's bytes are
+    written), with ERR_BAD_PARAM for what the call refuses."""
+    handle = lambda t: None if t is None else t.commit()._handle  # noqa: E731
+    sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+    addr = lambda b: b if b is None else _addr(b)  # noqa: E731
+    _lib.check(_lib.load().ompi_amd_ddt_sndrcv(addr(sbuf), scount, handle(sddt), addr(rbuf), rcount,
+                                                handle(rddt), sp), "ddt_sndrcv")
+
+
 class Convertor:
     """opal_convertor_t restricted to homogeneous device-buffer conversions."""
 
