@@ -88,14 +88,25 @@ int ompi_amd_comm_size(const ompi_amd_comm_t *comm);
  *   "force_shadow"  1: zero-copy calls treat every user buffer as one the
  *                   runtime refused to export and run through the export
  *                   fallback (a shadow copy of the communicator's own);
- *                   for tests */
+ *                   for tests
+ *   "osc_ddt_fuse"  1 (default): a one-sided call of this communicator's
+ *                   windows with a derived origin or result datatype
+ *                   (ompi_amd_osc.h's *_ddt calls) resolves every datatype
+ *                   in its one kernel; 0: the origin is packed into, and the
+ *                   result unpacked from, the window's scratch.  Read at
+ *                   every call; for tests and A/B timing */
 int ompi_amd_comm_set_param(ompi_amd_comm_t *comm, const char *key, int64_t value);
 /* Read a parameter above, or a state counter: "landing_bytes" (current
  * landing-buffer capacity), "landing_deferred_growths" (growths nonblocking
  * calls queued and progress completed), "landing_retired" (landing buffers
  * any growth replaced, kept until the communicator is destroyed), "imports" (this communicator's references to
  * peer mappings), "shadowed" (zero-copy calls that ran through the export
- * fallback), and the process-wide IPC registry's counters (mappings are
+ * fallback), the derived-datatype one-sided calls with a typed origin or
+ * result (calls whose origin and result are contiguous move none of these):
+ * "osc_ddt_fused" (ran with no packed stream), "osc_ddt_packed" (went
+ * through the window's scratch), "osc_ddt_lds" (fused launches with every
+ * typed side's program in LDS or registers), "osc_ddt_granule" (access
+ * width in bytes of the last fused put / get), and the process-wide IPC registry's counters (mappings are
  * shared by every communicator, window and message of the process and
  * closed with their last reference): "ipc_opens" / "ipc_closes" (runtime
  * open / close calls made), "ipc_shared" (maps answered from a mapping the

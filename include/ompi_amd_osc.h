@@ -130,7 +130,13 @@ int ompi_amd_get_accumulate(ompi_amd_win_t *win, const void *origin, void *resul
  * slots of tcount x tdt at the target (get_accumulate: the old elements are
  * returned into rcount x rdt at result first).  odt / rdt / tdt NULL: `type`
  * contiguous.  The three type signatures must hold the same number of
- * `type` elements; pair types (MAXLOC / MINLOC operands) only contiguous. */
+ * `type` elements; pair types (MAXLOC / MINLOC operands) only contiguous.
+ * One kernel under the target's accumulate lock resolves every side's
+ * datatype per element, the origin's and the result's included: nothing is
+ * packed or unpacked, and the origin is read while the lock is held.  Pair
+ * types with a derived origin or result, and every call under param
+ * "osc_ddt_fuse" = 0 of the window's communicator, go through a packed
+ * stream in the window's scratch instead (ompi_amd_coll.h: "osc_ddt_*"). */
 int ompi_amd_accumulate_ddt(ompi_amd_win_t *win, const void *origin, size_t ocount,
                             const ompi_amd_ddt_t *odt, int target, size_t disp, size_t tcount,
                             const ompi_amd_ddt_t *tdt, int type, int op, void *stream);
@@ -144,7 +150,10 @@ int ompi_amd_get_accumulate_ddt(ompi_amd_win_t *win, const void *origin, size_t 
  * layout at the target; only the target type's bytes are written, its gaps
  * keep theirs.  odt / tdt NULL: `ocount` / `tcount` contiguous bytes.  Both
  * sides must move the same number of bytes.  No accumulate lock (put and
- * get are not atomic); inside a passive epoch the epoch's lock gates it. */
+ * get are not atomic); inside a passive epoch the epoch's lock gates it.
+ * One launch in every case: with a datatype on both sides the kernel
+ * gathers through one and scatters through the other, with no packed copy
+ * between them (param "osc_ddt_fuse" = 0: the origin packed first). */
 int ompi_amd_put_ddt(ompi_amd_win_t *win, const void *origin, size_t ocount,
                      const ompi_amd_ddt_t *odt, int target, size_t disp, size_t tcount,
                      const ompi_amd_ddt_t *tdt, void *stream);

@@ -608,6 +608,7 @@ struct ompi_amd_comm {
     int win_shadow = 0;                   // param "osc_win_shadow": 1 = every MPI_Win_create shadowed (tests)
     int win_separate = 1;                 // param "osc_win_separate": 0 = refuse a window that needs a public copy
     int64_t shadow_windows = 0;           // MPI_Win_create windows in the separate model (osc_ipc.hip)
+    osc_ddt_stats osc_ddt;                // params "osc_ddt_*": derived-datatype RMA of this communicator's windows
     // param "user_ipc" (env OMPI_AMD_USER_IPC): export the caller's buffers
     // to peers (zero-copy).  Off by default: every zero-copy-size call stages
     // through the shadow arena (exported once, never freed), because on ROCm
@@ -3644,6 +3645,8 @@ int ompi_amd_comm_set_param(ompi_amd_comm_t *c, const char *key, int64_t v) {
         c->win_shadow = v ? 1 : 0;
     } else if (!strcmp(key, "osc_win_separate")) {
         c->win_separate = v ? 1 : 0;
+    } else if (!strcmp(key, "osc_ddt_fuse")) {
+        c->osc_ddt.fuse = v ? 1 : 0;
     } else if (!strcmp(key, "user_ipc")) {
         c->user_ipc = v ? 1 : 0;
         c->autotune = 0;
@@ -3774,6 +3777,11 @@ int ompi_amd_comm_get_param(const ompi_amd_comm_t *c, const char *key, int64_t *
     else if (!strcmp(key, "reuse_shadow")) *v = c->reuse_shadow;
     else if (!strcmp(key, "reused_exports")) *v = c->reused_exports;
     else if (!strcmp(key, "osc_shadow_windows")) *v = c->shadow_windows;
+    else if (!strcmp(key, "osc_ddt_fuse")) *v = c->osc_ddt.fuse;
+    else if (!strcmp(key, "osc_ddt_fused")) *v = c->osc_ddt.fused;
+    else if (!strcmp(key, "osc_ddt_packed")) *v = c->osc_ddt.packed;
+    else if (!strcmp(key, "osc_ddt_lds")) *v = c->osc_ddt.lds;
+    else if (!strcmp(key, "osc_ddt_granule")) *v = c->osc_ddt.granule;
     else if (!strcmp(key, "user_ipc")) *v = c->user_ipc;
     else if (!strcmp(key, "imports")) *v = (int64_t)c->imports.size();
     else if (!strncmp(key, "p2p_", 4) && p2p_get_param(c->p2p, key, v) == OMPI_AMD_SUCCESS) return OMPI_AMD_SUCCESS;
@@ -6339,6 +6347,8 @@ int comm_barrier(ompi_amd_comm_t *c, hipStream_t s) {
 int comm_sticky(ompi_amd_comm_t *c) { return check_sticky(c); }
 
 bool comm_typed_force64(const ompi_amd_comm_t *c) { return c->typed_force64 != 0; }
+
+osc_ddt_stats *comm_osc_ddt(ompi_amd_comm_t *c) { return &c->osc_ddt; }
 
 hipStream_t comm_call_stream(ompi_amd_comm_t *c, void *stream) { return comm_stream(c, stream); }
 

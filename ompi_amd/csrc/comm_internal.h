@@ -163,6 +163,17 @@ int xfer_pack_prog(const typed_prog &sp, const void *typed, void *dst, size_t by
                    typed_pick *pick);
 // param "typed_force64" of c
 bool comm_typed_force64(const ompi_amd_comm_t *c);
+// Params "osc_ddt_*" of a window's communicator (osc_ipc.hip's derived-datatype
+// RMA): the switch, and what the calls with a typed origin or
+// result did.  Calls whose origin and result are contiguous move none of them.
+struct osc_ddt_stats {
+    int fuse = 1;         // "osc_ddt_fuse": 0 takes the packed path (tests, A/B timing); read at every call
+    int64_t fused = 0;    // "osc_ddt_fused": calls that ran with no packed stream
+    int64_t packed = 0;   // "osc_ddt_packed": calls that went through the window's scratch
+    int64_t lds = 0;      // "osc_ddt_lds": fused launches with every typed side's program in LDS or registers
+    int64_t granule = 0;  // "osc_ddt_granule": access width of the last fused put / get
+};
+osc_ddt_stats *comm_osc_ddt(ompi_amd_comm_t *c);
 // Point-to-point mailboxes of the communicator (created with it).
 p2p_state *comm_p2p(ompi_amd_comm_t *c);
 // The one-sided part's per-communicator state (NULL until it sets one).

@@ -45,6 +45,7 @@
 
 #include "host_mark.h"
 #include "../../include/ompi_amd_osc.h"
+#include "coll_kernels.h"
 #include "comm_internal.h"
 #include "ddt_device.h"
 #include "ipc_registry.h"
@@ -636,6 +637,177 @@ __global__ __launch_bounds__(kOscThreads) void ddt_acc_kernel(ddt_desc d, char *
 using ddt_acc_fn = hipError_t (*)(dim3, const ddt_desc &, char *, const void *, void *, int64_t,
                                   const uint32_t *, bool, hipStream_t, int);
 
+// ---- a derived datatype on the origin side too ----
+// One side of the multi-sided element walk: the target, the origin or the
+// result of an accumulate, each with a program of its own or none.
+struct acc_side {
+    ddt_desc d;  // nelem 0: contiguous, element k at k * sizeof(T); sdiv: size / sizeof(T) (FAST)
+    char *p;     // the side's base (result: null when nothing is fetched)
+    int at;      // its program's first element in the kernel's LDS (-1: walked from global memory)
+    int copy;    // this side stages that copy (sides of one table share it)
+};
+// where the sides' programs sit: one element each, in registers; all in LDS;
+// or those that fit in LDS and the rest in global memory
+enum { ACC2_REG = 0, ACC2_LDS = 1, ACC2_MIXED = 2 };
+
+// ONE: the side's program is one element (a constant count lets the compiler
+// keep it in registers, as ddt_acc_kernel does for vectors).
+template <typename T, bool FAST, bool ONE>
+__device__ __forceinline__ int64_t acc2_offset(const acc_side &s, const ddt_elem *el, int64_t k) {
+    if (s.d.nelem == 0) return k * (int64_t)sizeof(T);  // wave-uniform
+    return acc_offset<T, FAST>(s.d, el, ONE ? 1 : s.d.nelem, k);
+}
+
+// ddt_acc_body with up to three typed sides: kAccUnroll elements per lane per
+// pass, every address first, then every load, then the stores.  old =
+// target[k]; result[roff(k)] = old when fetching; the target gets
+// f(old, origin[ooff(k)]) (OP 0: the origin's element, -1: nothing).
+template <typename T, int OP, bool FAST, bool ONE>
+__device__ __forceinline__ void ddt_acc2_body(const acc_side &tg, const ddt_elem *tel, const acc_side &og,
+                                              const ddt_elem *oel, const acc_side &rs, const ddt_elem *rel,
+                                              int64_t n) {
+    const int64_t chunk = (int64_t)kOscThreads * kAccUnroll;
+    const int64_t gs = (int64_t)gridDim.x * chunk;
+    const bool fetch = rs.p != nullptr;
+    for (int64_t b = (int64_t)blockIdx.x * chunk + threadIdx.x; b < n; b += gs) {
+        T *t[kAccUnroll], *r[kAccUnroll];
+        const T *o[kAccUnroll];
+        T v[kAccUnroll], x[kAccUnroll];
+#pragma unroll
+        for (int u = 0; u < kAccUnroll; ++u) {
+            const int64_t k = b + (int64_t)u * kOscThreads;
+            t[u] = nullptr;
+            if (k < n) {
+                t[u] = reinterpret_cast<T *>(tg.p + acc2_offset<T, FAST, ONE>(tg, tel, k));
+                if constexpr (OP >= 0)
+                    o[u] = reinterpret_cast<const T *>(og.p + acc2_offset<T, FAST, ONE>(og, oel, k));
+                if (fetch) r[u] = reinterpret_cast<T *>(rs.p + acc2_offset<T, FAST, ONE>(rs, rel, k));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kAccUnroll; ++u) {
+            if (!t[u]) continue;
+            v[u] = *t[u];
+            if constexpr (OP >= 0) x[u] = *o[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kAccUnroll; ++u) {
+            if (!t[u]) continue;
+            if (fetch) *r[u] = v[u];
+            if constexpr (OP == 0) {
+                *t[u] = x[u];
+            } else if constexpr (OP > 0) {
+                store_elem(t[u], opfn<OP, false>::f(v[u], x[u]));
+            }
+        }
+    }
+}
+
+// The staged copy of one side's program (by the whole workgroup).
+__device__ __forceinline__ void acc2_stage(ddt_elem *lds, const acc_side &s) {
+    if (s.d.nelem > 0 && s.at >= 0 && s.copy)
+        lds_words(lds + s.at, s.d.elems, s.d.nelem * (int)(sizeof(ddt_elem) / sizeof(uint64_t)));
+}
+
+// Accumulate / get_accumulate with a derived datatype on the origin or the
+// result (and any target): no packed stream on either.  Whether a side is
+// typed is a runtime branch, so the kernel has ddt_acc_kernel's instantiations
+// and no more.  One LDS array serves all sides (the host lays it out,
+// smallest program first, one copy per table); what does not fit is read
+// from global memory through flat loads (ACC2_MIXED: a table past
+// kDdtLdsElems, rare enough not to specialise).
+template <typename T, int OP, bool FAST>
+__global__ __launch_bounds__(kOscThreads) void ddt_acc2_kernel(acc_side tg, acc_side og, acc_side rs,
+                                                               int64_t n, const uint32_t *gate, int mode,
+                                                               int sys) {
+    if (!gate_open(gate)) return;
+    __shared__ ddt_elem lds[kDdtLdsElems];
+    if (threadIdx.x == 0) osc_acquire();
+    if (mode == ACC2_REG) {
+        ddt_elem et{}, eo{}, er{};
+        if (tg.d.nelem) et = tg.d.elems[0];
+        if (og.d.nelem) eo = og.d.elems[0];
+        if (rs.d.nelem) er = rs.d.elems[0];
+        __syncthreads();
+        ddt_acc2_body<T, OP, FAST, true>(tg, &et, og, &eo, rs, &er, n);
+    } else {
+        acc2_stage(lds, tg);
+        acc2_stage(lds, og);
+        acc2_stage(lds, rs);
+        __syncthreads();
+        if (mode == ACC2_LDS)
+            ddt_acc2_body<T, OP, FAST, false>(tg, lds + tg.at, og, lds + og.at, rs, lds + rs.at, n);
+        else
+            ddt_acc2_body<T, OP, FAST, false>(tg, tg.at >= 0 ? lds + tg.at : tg.d.elems, og,
+                                              og.at >= 0 ? lds + og.at : og.d.elems, rs,
+                                              rs.at >= 0 ? lds + rs.at : rs.d.elems, n);
+    }
+    if (sys) osc_epilogue();  // sys: the target or the result is not this GPU's memory
+}
+
+using ddt_acc2_fn = hipError_t (*)(dim3, const acc_side &, const acc_side &, const acc_side &, int64_t,
+                                   const uint32_t *, bool, int, hipStream_t, int);
+// an (op, type) slot's two launchers: the target-only walk and the multi-sided one
+struct ddt_acc_fns {
+    ddt_acc_fn one = nullptr;
+    ddt_acc2_fn multi = nullptr;
+};
+
+// Which of the two programs a two-ended launch stages (xfer_sndrcv's rule).
+enum { D2_LDS_SRC = 1, D2_LDS_DST = 2, D2_LDS_SAME = 4 };
+
+// Put / get between two derived datatypes in one gated launch: stream bytes
+// gathered through se based at sb and scattered through de based at db, each
+// workgroup its a2a_slice of the stream.  Put: sb the origin, db the mapped
+// window; get the reverse.  sys: db is not this GPU's memory, the workgroup's
+// stores end with a system-scope release (typed_walk2's stores are plain).
+__global__ __launch_bounds__(kXferThreads) void rma_ddt2_kernel(typed_end se, typed_end de, int lds,
+                                                                const char *sb, char *db, int64_t bytes,
+                                                                int force64, const uint32_t *gate, int sys) {
+    if (!gate_open(gate)) return;
+    __shared__ ddt_elem prog[kDdtLdsElems];
+    if (threadIdx.x == 0) osc_acquire();
+    constexpr int W = (int)(sizeof(ddt_elem) / sizeof(uint64_t));
+    typed_end s = se, d = de;
+    if (lds & D2_LDS_SRC) {
+        lds_words(prog, se.d.elems, se.d.nelem * W);
+        s.d.elems = prog;
+    }
+    if (lds & D2_LDS_SAME) {
+        d.d.elems = prog;
+    } else if (lds & D2_LDS_DST) {
+        ddt_elem *at = prog + ((lds & D2_LDS_SRC) ? se.d.nelem : 0);
+        lds_words(at, de.d.elems, de.d.nelem * W);
+        d.d.elems = at;
+    }
+    __syncthreads();
+    int64_t lo, hi;
+    a2a_slice(bytes, (int)blockIdx.x, (int)gridDim.x, &lo, &hi);
+    typed_pipe_copy2(s, d, sb, db, lo, hi, bytes, force64 != 0);
+    if (sys) osc_epilogue();
+}
+
+// A derived origin against a contiguous target: the one-ended walk straight
+// between the origin's layout and the window (UNPACK: a get).
+template <bool UNPACK>
+__global__ __launch_bounds__(kXferThreads) void rma_ddt1_kernel(typed_end oe, int lds, char *typed, char *contig,
+                                                                int64_t bytes, int force64,
+                                                                const uint32_t *gate, int sys) {
+    if (!gate_open(gate)) return;
+    __shared__ ddt_elem prog[kDdtLdsElems];
+    if (threadIdx.x == 0) osc_acquire();
+    typed_end e = oe;
+    if (lds) {
+        lds_words(prog, oe.d.elems, oe.d.nelem * (int)(sizeof(ddt_elem) / sizeof(uint64_t)));
+        e.d.elems = prog;
+    }
+    __syncthreads();
+    int64_t lo, hi;
+    a2a_slice(bytes, (int)blockIdx.x, (int)gridDim.x, &lo, &hi);
+    typed_pipe_copy<UNPACK>(e, typed, contig, lo, hi, bytes, false, force64 != 0);
+    if (sys) osc_epilogue();
+}
+
 // ---- derived datatypes of pair type (MAXLOC / MINLOC operands) ----
 // ompi_osc_base_sndrcv_op (osc_base_obj_convert.c:73-245) converts the
 // origin into the target's primitive slots element by element; a pair's
@@ -750,20 +922,33 @@ static hipError_t ddt_acc_launch(dim3 grid, const ddt_desc &d, char *typed, cons
                            static_cast<const T *>(in), static_cast<T *>(old), n, gate, sys);
     return hipGetLastError();
 }
-template <int OP, int TYPE>
-static constexpr ddt_acc_fn ddt_acc_slot() {
-    if constexpr (slot_supported(OP, TYPE) && !is_pair_type(TYPE))
-        return &ddt_acc_launch<typename type_of<TYPE>::type, OP>;
+template <typename T, int OP>
+static hipError_t ddt_acc2_launch(dim3 grid, const acc_side &tg, const acc_side &og, const acc_side &rs,
+                                  int64_t n, const uint32_t *gate, bool fast, int mode, hipStream_t s,
+                                  int sys) {
+    if (fast)  // every typed side's d.sdiv holds its size / sizeof(T)
+        hipLaunchKernelGGL((ddt_acc2_kernel<T, OP, true>), grid, dim3(kOscThreads), 0, s, tg, og, rs, n, gate,
+                           mode, sys);
     else
-        return nullptr;
+        hipLaunchKernelGGL((ddt_acc2_kernel<T, OP, false>), grid, dim3(kOscThreads), 0, s, tg, og, rs, n, gate,
+                           mode, sys);
+    return hipGetLastError();
+}
+template <int OP, int TYPE>
+static constexpr ddt_acc_fns ddt_acc_slot() {
+    if constexpr (slot_supported(OP, TYPE) && !is_pair_type(TYPE))
+        return {&ddt_acc_launch<typename type_of<TYPE>::type, OP>,
+                &ddt_acc2_launch<typename type_of<TYPE>::type, OP>};
+    else
+        return {};
 }
 template <int OP, int... T>
-static constexpr std::array<ddt_acc_fn, OMPI_AMD_TYPE_COUNT> make_ddt_acc_row(
+static constexpr std::array<ddt_acc_fns, OMPI_AMD_TYPE_COUNT> make_ddt_acc_row(
     std::integer_sequence<int, T...>) {
     return {{ddt_acc_slot<OP, T>()...}};
 }
 template <int... O>
-static constexpr std::array<std::array<ddt_acc_fn, OMPI_AMD_TYPE_COUNT>, OMPI_AMD_OP_COUNT>
+static constexpr std::array<std::array<ddt_acc_fns, OMPI_AMD_TYPE_COUNT>, OMPI_AMD_OP_COUNT>
 make_ddt_acc_table(std::integer_sequence<int, O...>) {
     return {{make_ddt_acc_row<O>(std::make_integer_sequence<int, OMPI_AMD_TYPE_COUNT>{})...}};
 }
@@ -776,12 +961,15 @@ template <> struct sized<2> { using t = uint16_t; };
 template <> struct sized<4> { using t = uint32_t; };
 template <> struct sized<8> { using t = uint64_t; };
 template <> struct sized<16> { typedef unsigned int t __attribute__((ext_vector_type(4))); };
-static ddt_acc_fn ddt_rw_fn(size_t size, bool replace) {
+static ddt_acc_fns ddt_rw_fn(size_t size, bool replace) {
     switch (size) {
-#define RW(SZ) case SZ: return replace ? &ddt_acc_launch<sized<SZ>::t, 0> : &ddt_acc_launch<sized<SZ>::t, -1>;
+#define RW(SZ)                                                                                            \
+    case SZ:                                                                                              \
+        return replace ? ddt_acc_fns{&ddt_acc_launch<sized<SZ>::t, 0>, &ddt_acc2_launch<sized<SZ>::t, 0>} \
+                       : ddt_acc_fns{&ddt_acc_launch<sized<SZ>::t, -1>, &ddt_acc2_launch<sized<SZ>::t, -1>};
         RW(1) RW(2) RW(4) RW(8) RW(16)
 #undef RW
-    default: return nullptr;
+    default: return {};
     }
 }
 
@@ -1075,7 +1263,7 @@ int64_t osc_grid_cap() {
 // 0.722 of 8 TB/s, profiles/r03_xfer_probe.jsonl).  The limit is the grid:
 // one chunk per workgroup reaches 0.775 without an acquire but 0.456 with
 // one per workgroup, so the persistent grid (one acquire per CU) stays.
-constexpr int kXferThreads = 256, kXferUnroll = 4;
+constexpr int kXferUnroll = 4;  // kXferThreads: coll_kernels.h
 
 int xfer_copy(const void *src, void *dst, size_t bytes, hipStream_t s, const uint32_t *gate,
               bool remote_dst) {
@@ -1913,7 +2101,10 @@ int ompi_amd_get_accumulate(ompi_amd_win_t *w, const void *origin, void *result,
 }
 
 // Derived datatypes on any side (osc_sm_comm.c:135, 191, 301, 350 ->
-// ompi_osc_base_sndrcv_op): a non-contiguous origin is packed on the
+// ompi_osc_base_sndrcv_op).  A derived origin or result runs acc_ddt_fused
+// below (one kernel over every side's program); what follows
+// is the packed path that pair types and param osc_ddt_fuse = 0 keep, and a
+// contiguous origin and result with a derived target: a non-contiguous origin is packed on the
 // device first (local, before the lock); under the target's accumulate
 // lock one gated kernel walks the target datatype's element slots, fetching
 // the old elements packed (get_accumulate) and combining the packed origin
@@ -1991,7 +2182,94 @@ static int acc_ddt_pair(ompi_amd_win_t *w, const void *origin, size_t ocount, co
         rc = ompi_amd_ddt_unpack(rdt, rcount, pr, result, 0, tsig, &done, s);
         if (rc == OMPI_AMD_SUCCESS && done != tsig) rc = OMPI_AMD_ERR_BAD_PARAM;
     }
-    if (po || pr) osc_scratch_done(w, s);
+    if (po || pr) {
+        osc_scratch_done(w, s);
+        ++comm_osc_ddt(w->c)->packed;
+    }
+    return rc;
+}
+
+// OMPI_AMD_OSC_DDT_FAST=0 (read once): every derived-datatype walk of the
+// one-sided calls in 64-bit arithmetic.
+static bool osc_ddt_fast_on() {
+    static const bool on = !(getenv("OMPI_AMD_OSC_DDT_FAST") && atoi(getenv("OMPI_AMD_OSC_DDT_FAST")) == 0);
+    return on;
+}
+
+// The derived-datatype walks' persistent grid (p2p_typed.hip's typed_blocks):
+// one pass of a workgroup at G = 16 per block, under the byte copies' cap.
+static unsigned ddt2_blocks(size_t bytes) {
+    const int64_t per = (int64_t)kXferThreads * kDdtUnroll * 16;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)bytes + per - 1) / per, osc_grid_cap()));
+}
+
+// One side of ddt_acc2_kernel from the caller's (buffer, datatype): *fast
+// stays true while the side passes the test acc_ddt applies to the target.
+static bool acc_side_of(const ompi_amd_ddt_t *ddt, const void *p, int64_t e, bool *fast, acc_side *out) {
+    *out = acc_side{ddt_desc{}, static_cast<char *>(const_cast<void *>(p)), -1, 0};
+    if (!ddt) return true;  // contiguous
+    ddt_view v{};
+    if (!ddt_view_of(ddt, &v) || v.d.nelem <= 0) return false;
+    out->d = v.d;
+    if (v.gran % e == 0 && v.d.size / e < (1ll << 32) && v.max_blen / e < (1ll << 32))
+        out->d.sdiv = make_fdiv((uint32_t)(v.d.size / e));
+    else
+        *fast = false;
+    return true;
+}
+
+// acc_ddt with a derived origin or result, no packed stream: lock, one
+// launch of ddt_acc2_kernel over every side's program, unlock.  The origin is
+// gathered under the target's accumulate lock (the packed path gathers it
+// before the lock).  t: the target's base (target_span).
+static int acc_ddt_fused(ompi_amd_win_t *w, const void *origin, const ompi_amd_ddt_t *odt, void *result,
+                         const ompi_amd_ddt_t *rdt, int target, char *t, const ompi_amd_ddt_t *tdt,
+                         int64_t ext, int64_t n, ddt_acc2_fn f, bool has_origin, hipStream_t s) {
+    bool fast = osc_ddt_fast_on() && (ext == 1 || ext == 2 || ext == 4 || ext == 8 || ext == 16) &&
+                n < (1ll << 32);
+    acc_side sd[3];  // target, origin, result
+    if (!acc_side_of(tdt, t, ext, &fast, &sd[0]) ||
+        !acc_side_of(has_origin ? odt : nullptr, has_origin ? origin : nullptr, ext, &fast, &sd[1]) ||
+        !acc_side_of(result ? rdt : nullptr, result, ext, &fast, &sd[2]))
+        return OMPI_AMD_ERR_BAD_PARAM;
+    // the LDS layout: one copy per table, smallest first, while they fit
+    int order[3] = {0, 1, 2}, mode = ACC2_REG, used = 0;
+    std::sort(order, order + 3, [&](int a, int b) { return sd[a].d.nelem < sd[b].d.nelem; });
+    bool all_lds = true;
+    for (int i = 0; i < 3; ++i) {
+        acc_side &x = sd[order[i]];
+        if (x.d.nelem == 0) continue;
+        if (x.d.nelem != 1) mode = ACC2_LDS;
+        bool shared = false;
+        for (int j = 0; j < i; ++j)
+            if (sd[order[j]].d.elems == x.d.elems) {  // one table, one copy (or none)
+                x.at = sd[order[j]].at;
+                shared = true;
+            }
+        if (!shared && used + x.d.nelem <= kDdtLdsElems) {
+            x.at = used;
+            x.copy = 1;
+            used += x.d.nelem;
+        }
+        all_lds = all_lds && x.at >= 0;
+    }
+    if (mode == ACC2_LDS && !all_lds) mode = ACC2_MIXED;
+    if (mode == ACC2_LDS)  // a side without a program reads nothing at lds + 0
+        for (acc_side &x : sd) x.at = std::max(x.at, 0);
+    osc_ddt_stats *st = comm_osc_ddt(w->c);
+    int rc = launch_lock(w, target, 0, s);
+    if (rc == OMPI_AMD_SUCCESS) {
+        const int64_t blocks = std::max<int64_t>(
+            1, std::min<int64_t>((n + kOscThreads * kAccUnroll - 1) / (kOscThreads * kAccUnroll), osc_grid_cap()));
+        const bool sys = remote_dst(w, target) || (result && !on_this_device(result, comm_device(w->c)));
+        rc = record_hip(f(dim3((unsigned)blocks), sd[0], sd[1], sd[2], n, taken_word(w, target, true), fast, mode,
+                          s, sys ? 1 : 0),
+                        "osc derived accumulate launch (typed origin / result)");
+        const int urc = launch_lock(w, target, 1, s);  // always release
+        if (rc == OMPI_AMD_SUCCESS) rc = urc;
+        ++st->fused;
+        st->lds += mode != ACC2_MIXED ? 1 : 0;
+    }
     return rc;
 }
 
@@ -2016,9 +2294,10 @@ static int acc_ddt(ompi_amd_win_t *w, const void *origin, size_t ocount, const o
     }
     const int64_t n = (int64_t)(tbytes / ext);
     if (!tdt && !odt && !rdt) return rma_op(w, origin, result, (size_t)n, type, target, disp, op, stream);
-    ddt_acc_fn f = nullptr;
-    if (op == OMPI_AMD_OP_REPLACE || op == OMPI_AMD_OP_NO_OP) f = ddt_rw_fn(ext, op == OMPI_AMD_OP_REPLACE);
-    else if (op > 0 && op < OMPI_AMD_OP_COUNT) f = g_ddt_acc[op][type];
+    ddt_acc_fns fns;
+    if (op == OMPI_AMD_OP_REPLACE || op == OMPI_AMD_OP_NO_OP) fns = ddt_rw_fn(ext, op == OMPI_AMD_OP_REPLACE);
+    else if (op > 0 && op < OMPI_AMD_OP_COUNT) fns = g_ddt_acc[op][type];
+    const ddt_acc_fn f = fns.one;
     if (!f || (op != OMPI_AMD_OP_REPLACE && op != OMPI_AMD_OP_NO_OP && !g_acc[op][type])) {
         record_msg("osc accumulate: op %d on type %d is not provided", op, type);
         return OMPI_AMD_ERR_UNSUPPORTED;
@@ -2035,6 +2314,11 @@ static int acc_ddt(ompi_amd_win_t *w, const void *origin, size_t ocount, const o
     OSC_TRY(target_span(w, target, base, lo - base, hi - base, &t));
     hipStream_t s = win_stream(w, stream);
     OSC_TRY(record_hip(hipSetDevice(comm_device(w->c)), "hipSetDevice"));
+    // a typed origin or result: every side resolved in one kernel, unless param osc_ddt_fuse = 0
+    const bool has_origin = op != OMPI_AMD_OP_NO_OP;
+    if (((odt && has_origin) || (fetch && rdt)) && comm_osc_ddt(w->c)->fuse)
+        return acc_ddt_fused(w, origin, odt, result, rdt, target, t, tdt, (int64_t)ext, n, fns.multi, has_origin,
+                             s);
     // origin stream, packed (local; before the lock)
     const void *in = origin;
     void *po = nullptr, *pr = nullptr;
@@ -2062,9 +2346,7 @@ static int acc_ddt(ompi_amd_win_t *w, const void *origin, size_t ocount, const o
             // run, displacement and stride is a multiple of the element
             ddt_desc dd = tv.d;
             const int64_t e = (int64_t)ext;
-            static const bool fast_on = !(getenv("OMPI_AMD_OSC_DDT_FAST") &&
-                                          atoi(getenv("OMPI_AMD_OSC_DDT_FAST")) == 0);
-            const bool fast = fast_on && (e == 1 || e == 2 || e == 4 || e == 8 || e == 16) && tv.gran % e == 0 &&
+            const bool fast = osc_ddt_fast_on() && (e == 1 || e == 2 || e == 4 || e == 8 || e == 16) && tv.gran % e == 0 &&
                               n < (1ll << 32) && dd.size / e < (1ll << 32) && tv.max_blen / e < (1ll << 32);
             if (fast) dd.sdiv = make_fdiv((uint32_t)(dd.size / e));
             rc = record_hip(f(dim3((unsigned)blocks), dd, t, in, old, n, gate, fast, s,
@@ -2086,15 +2368,63 @@ static int acc_ddt(ompi_amd_win_t *w, const void *origin, size_t ocount, const o
         rc = ompi_amd_ddt_unpack(rdt, rcount, pr, result, 0, tbytes, &done, s);
         if (rc == OMPI_AMD_SUCCESS && done != tbytes) rc = OMPI_AMD_ERR_BAD_PARAM;
     }
-    if (po || pr) osc_scratch_done(w, s);
+    if (po || pr) {
+        osc_scratch_done(w, s);
+        ++comm_osc_ddt(w->c)->packed;
+    }
     return rc;
 }
 
+// rma_ddt with a derived origin, no packed stream: one gated
+// launch between the origin's layout and the window — rma_ddt2_kernel through
+// both programs, or the one-ended walk when the target is contiguous (tv
+// null).  t: the target's base (target_span); bytes: the stream.
+static int rma_ddt_fused(ompi_amd_win_t *w, char *origin, const ompi_amd_ddt_t *odt, int target, char *t,
+                         const ddt_view *tv, size_t bytes, bool put, const uint32_t *gate, hipStream_t s) {
+    ddt_view ov{};
+    if (!ddt_view_of(odt, &ov) || ov.d.nelem <= 0) return OMPI_AMD_ERR_BAD_PARAM;
+    const bool sys = put ? remote_dst(w, target) : !on_this_device(origin, comm_device(w->c));
+    const bool force64 = !osc_ddt_fast_on();
+    const int K = kDdtLdsElems, no = ov.d.nelem;
+    osc_ddt_stats *st = comm_osc_ddt(w->c);
+    const dim3 grid(ddt2_blocks(bytes)), block(kXferThreads);
+    if (!tv) {
+        // the 32-bit walk divides by size / G: a stream that ends inside a huge element takes the 64-bit one
+        const int f64 = (force64 || (uint64_t)ov.d.size >= (1ull << 32)) ? 1 : 0;
+        const int lds = no <= K;
+        if (put)
+            hipLaunchKernelGGL(rma_ddt1_kernel<false>, grid, block, 0, s, end_of(true, ov), lds, origin, t,
+                               (int64_t)bytes, f64, gate, sys ? 1 : 0);
+        else
+            hipLaunchKernelGGL(rma_ddt1_kernel<true>, grid, block, 0, s, end_of(true, ov), lds, origin, t,
+                               (int64_t)bytes, f64, gate, sys ? 1 : 0);
+        st->lds += lds;
+        st->granule = typed_granule(ov.gran, (uint64_t)(uintptr_t)origin, (uint64_t)(uintptr_t)t);
+    } else {
+        // both in LDS when they fit together (one copy when they are one program);
+        // otherwise the smaller one is staged and the larger walked from global memory
+        const int nt = tv->d.nelem;
+        int lds = 0;
+        if (ov.d.elems == tv->d.elems) lds = no <= K ? D2_LDS_SRC | D2_LDS_SAME : 0;
+        else if (no + nt <= K) lds = D2_LDS_SRC | D2_LDS_DST;
+        else if (std::min(no, nt) <= K) lds = (put ? no <= nt : nt <= no) ? D2_LDS_SRC : D2_LDS_DST;
+        const typed_end oe = end_of(true, ov), te = end_of(true, *tv);
+        hipLaunchKernelGGL(rma_ddt2_kernel, grid, block, 0, s, put ? oe : te, put ? te : oe, lds,
+                           put ? origin : t, put ? t : origin, (int64_t)bytes, force64 ? 1 : 0, gate, sys ? 1 : 0);
+        st->lds += ((lds & D2_LDS_SRC) && (lds & (D2_LDS_DST | D2_LDS_SAME))) ? 1 : 0;
+        st->granule = typed_granule2(ov.gran, tv->gran, (uint64_t)(uintptr_t)origin, (uint64_t)(uintptr_t)t, 0);
+    }
+    ++st->fused;
+    return record_hip(hipGetLastError(), put ? "osc derived put launch (typed origin)"
+                                             : "osc derived get launch (typed origin)");
+}
+
 // MPI_Put / MPI_Get with derived datatypes (osc_sm_comm.c:24-100, 209-270:
-// ompi_datatype_sndrcv of any origin / target pair).  The origin side is a
+// ompi_datatype_sndrcv of any origin / target pair).  A derived origin moves
+// in rma_ddt_fused above; with param osc_ddt_fuse = 0 it is a
 // packed byte stream on this GPU (a non-contiguous origin is packed before
-// a put, and unpacked from it after a get, by the convertor's kernels); the
-// target side moves in one launch of ddt_acc_kernel over G-byte granules (G
+// a put, and unpacked from it after a get, by the convertor's kernels).  The
+// target side of a contiguous or packed origin moves in one launch of ddt_acc_kernel over G-byte granules (G
 // the widest power of two dividing every run, displacement, stride and
 // extent of the target type and both addresses): REPLACE stores granule k
 // of the stream into the k-th granule slot of the target type, NO_OP loads
@@ -2130,6 +2460,9 @@ static int rma_ddt(ompi_amd_win_t *w, void *origin, size_t ocount, const ompi_am
     hipStream_t s = win_stream(w, stream);
     OSC_TRY(record_hip(hipSetDevice(comm_device(w->c)), "hipSetDevice"));
     const uint32_t *gate = epoch_gate(w, target);
+    if (odt && comm_osc_ddt(w->c)->fuse)
+        return rma_ddt_fused(w, static_cast<char *>(origin), odt, target, t, tdt ? &tv : nullptr, tbytes, put, gate,
+                             s);
     int rc = OMPI_AMD_SUCCESS;
     char *packed = static_cast<char *>(origin);
     void *tmp = nullptr;
@@ -2149,7 +2482,7 @@ static int rma_ddt(ompi_amd_win_t *w, void *origin, size_t ocount, const ompi_am
         int64_t g = tv.gran;
         while (g > 1 && (((uintptr_t)t | (uintptr_t)packed) & (uintptr_t)(g - 1))) g >>= 1;
         g = std::min<int64_t>(g, 16);
-        const ddt_acc_fn f = ddt_rw_fn((size_t)g, put);
+        const ddt_acc_fn f = ddt_rw_fn((size_t)g, put).one;
         const int64_t n = (int64_t)tbytes / g;
         const int64_t blocks = std::max<int64_t>(
             1, std::min<int64_t>((n + kOscThreads * kAccUnroll - 1) / (kOscThreads * kAccUnroll),
@@ -2168,7 +2501,10 @@ static int rma_ddt(ompi_amd_win_t *w, void *origin, size_t ocount, const ompi_am
         rc = ompi_amd_ddt_unpack(odt, ocount, tmp, origin, 0, tbytes, &done, s);
         if (rc == OMPI_AMD_SUCCESS && done != tbytes) rc = OMPI_AMD_ERR_BAD_PARAM;
     }
-    if (tmp) osc_scratch_done(w, s);
+    if (tmp) {
+        osc_scratch_done(w, s);
+        ++comm_osc_ddt(w->c)->packed;
+    }
     return rc;
 }
 
